@@ -17,7 +17,15 @@ steps, inside the timed region (--gather-mode blocking / none: the A/B legs of t
 
 Rank 0 prints ONE JSON line (see the driver contract), including
   roofline     : HBM roofline of the step kernel from HIP-event timings taken on the engine's launch stream
-  cpu_baseline : the float64 CPU oracle timed on this box's host cores on a bounded sample (rank 0, N = 1 only)
+A plain run does only what that line's headline figure needs: set-up, --warmup steps, the --steps timed steps, the outputs
+(--dump-outputs DIR) and the line.  --full adds the measurements that take runs of their own (rank 0, N = 1 only):
+  cpu_baseline       : the float64 CPU oracle timed on this box's host cores on a bounded sample
+  single_step_launch : the same loop as one kernel launch per control step, timed after the contract region
+  roofline.peak_measured_triad : a device triad that calibrates the roofline's denominator (before the warm-up)
+
+--dump-outputs DIR writes what the timed path computed in its last step -- the arrays a caller of the engine would receive
+(observation, reward, done, state) -- as DIR/<name>.npy in float32 / float64, at most 64 MB in all (a fixed
+seeded sample of env rows when the batch is larger).  Inputs are seeded: the same arguments give the same inputs in every run.
 """
 import argparse
 import json
@@ -42,6 +50,27 @@ GAMMA, LAMBDA = 0.95, 0.95              # example_pmc_train.sh:21-22
 
 PMC_REWARD_WEIGHTS = {'joint_pos': 0.3, 'joint_vel': 0.05, 'end_effector': 0.1, 'root_pose': 0.5, 'root_vel': 0.05}
 PMC_PROP_TYPE = ['joint_pos', 'joint_vel', 'root_ang_vel_loc', 'root_lin_vel_loc', 'e_g']
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, arrays):
+    """Write {name: array} as out_dir/<name>.npy: float64 stays float64, everything else becomes float32.  Every array's first axis is the
+    env (or arena) axis; if the whole set is larger than DUMP_LIMIT_BYTES, the same fixed, seeded sample of rows is taken from every array."""
+    arrays = {k: np.ascontiguousarray(v, dtype=np.float64 if np.asarray(v).dtype == np.float64 else np.float32) for k, v in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    rows = None
+    if total > DUMP_LIMIT_BYTES:
+        n = min(a.shape[0] for a in arrays.values())
+        keep = max(1, int((DUMP_LIMIT_BYTES - 4096 * (len(arrays) + 1)) / (total / n + 8)))      # (+ 8 bytes a row for sampled_rows.npy, + the .npy headers)
+        rows = np.sort(np.random.default_rng(0).choice(n, size=keep, replace=False))
+        arrays = {k: a[rows] for k, a in arrays.items()}
+    os.makedirs(out_dir, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(out_dir, k + '.npy'), a)
+    if rows is not None:
+        np.save(os.path.join(out_dir, 'sampled_rows.npy'), rows.astype(np.float64))
 
 
 def build_record():
@@ -240,8 +269,12 @@ def main():
     ap.add_argument('--steps', type=int, default=2000)
     ap.add_argument('--warmup', type=int, default=200)
     ap.add_argument('--envs-per-gpu', type=int, default=ENVS_PER_GPU)
-    ap.add_argument('--no-cpu-baseline', action='store_true')
-    ap.add_argument('--no-single-step-leg', action='store_true', help='skip the secondary one-launch-per-control-step measurement (N = 1)')
+    ap.add_argument('--full', action='store_true',
+                    help='also measure what takes runs of its own: the CPU baseline, the one-launch-per-control-step leg (pmc) and the HBM triad (pmc); N = 1 only')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='with --full: skip the CPU baseline')
+    ap.add_argument('--no-single-step-leg', action='store_true', help='with --full: skip the secondary one-launch-per-control-step measurement (N = 1)')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help="write what the timed path computed in its last step as DIR/<name>.npy (rank 0's engine; float32 / float64, at most 64 MB)")
     ap.add_argument('--workload', choices=['pmc', 'epmc', 'sepmc'], default='pmc',
                     help="pmc = BASELINE config 2 (the contract line); epmc = config 4 (PlayGroundEnv, DESIGN.md 8), sepmc = config 5 (ChaseTagGameEnv, 2048 arenas x 2 robots, DESIGN.md 8b), same JSON shape")
     ap.add_argument('--element', type=int, default=1, help='epmc only: env_randomize_config element_id (0 joystick, 1 hurdles, 2 holes, 3 cubes)')
@@ -363,7 +396,7 @@ def main_pmc(args):
     # The calibration runs BEFORE the warm-up and the timed region (LL_BENCH_TRIAD_FIRST=0: after): a driver-style run of 25 control steps is
     # 4 ms of GPU work from a cold device; with 40 ms of triad in front the same 20 timed steps run 2 % faster (profiles/r03_driver_style.txt)
     triad_first = os.environ.get('LL_BENCH_TRIAD_FIRST', '1') == '1'
-    triad = measure_triad() if triad_first else None
+    triad = measure_triad() if (args.full and triad_first) else None
 
     n_done = [0]                                           # control steps executed so far == the engine's step index
     spl = max(1, args.steps_per_launch)
@@ -451,6 +484,9 @@ def main_pmc(args):
                 got_sig = [[float(g.sum()), float(g.abs().sum()), float(g[0, 0, 0]), float(g[-1, -1, -1]), float(g[n // 2, UNROLL // 2, 207])] for g in got]
                 gather_check = 'ok' if got_sig == sigs and len({tuple(x) for x in sigs}) == world else 'MISMATCH %r vs %r' % (got_sig, sigs)
     set_phase('report')
+    if args.dump_outputs and rank == 0:
+        r_, d_, _ = eng.reward_done()
+        dump_outputs(args.dump_outputs, {'obs': eng.obs(), 'reward': r_, 'done': d_, 'state': eng.state()})
     counters = eng.counters()
     stale_reseeds = eng.table_sync()                         # (before the single-step leg; 0 unless the chip was shared: ll_get_table_sync)
     ep_hist = [int(x) for x in eng.episode_histogram()]
@@ -458,7 +494,7 @@ def main_pmc(args):
     # runs, and what rounds 1-2 reported; the prioritized-sampling table is folded after every step, as PLE:235-240 does.  Measured after the
     # contract region on the same engine (N = 1 only; a short region of its own), reported beside `value`, never instead of it.
     single = None
-    if not multi and spl > 1 and not args.no_single_step_leg:
+    if args.full and not multi and spl > 1 and not args.no_single_step_leg:
         ks = max(1, min(args.steps, 200))
         for _ in range(5):
             eng.step_random(SIGMA)
@@ -474,7 +510,7 @@ def main_pmc(args):
         single = {'value': n * ks / ts, 'unit': 'env-steps/s', 'steps': ks, 'ms_per_step': ts / ks * 1e3, 'kernel_avg_ms': s_launch_ms,
                   'note': 'one kernel launch per control step (ll_step_random), the sampling table folded after every step: the loop an actor with a '
                           'policy between the steps runs'}
-    if triad is None and not triad_first:
+    if args.full and triad is None and not triad_first:
         triad = measure_triad()
 
     if rank == 0:
@@ -521,7 +557,7 @@ def main_pmc(args):
                          'frac': (achieved / HBM_PEAK_GBPS) if achieved else None,
                          # per launch like `achieved`: the committed counter passes ran launches of `spl` control steps; this run's launches average cspl
                          'traffic': (traffic / spl * cspl) if traffic else None, 'traffic_per_control_step': (traffic / spl) if traffic else None,
-                         'algorithmic_bytes_per_launch': n * algo_bytes * cspl, 'peak_measured_triad': triad, 'peak_measured_triad_when': 'before the warm-up steps' if triad_first else 'after the timed region',
+                         'algorithmic_bytes_per_launch': n * algo_bytes * cspl, 'peak_measured_triad': triad, 'peak_measured_triad_when': ('before the warm-up steps' if triad_first else 'after the timed region') if args.full else 'not measured (bench.py --full)',
                          'traffic_source': tsrc,
                          'kernel': 'pmc_step_kernel', 'kernel_avg_ms': k_ms, 'kernel_launches_timed': k_n,
                          'kernel_avg_launch_ms': k_launch_ms, 'control_steps_per_launch': (k_steps / k_n) if k_n else None,
@@ -531,7 +567,7 @@ def main_pmc(args):
         out['build'] = build_record()
         if single is not None:
             out['single_step_launch'] = single
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out['cpu_baseline'] = cpu_baseline(blob, table)
         print(json.dumps(out), flush=True)
     if traj is not None:
@@ -628,6 +664,9 @@ def main_epmc(args):
         tt = torch.tensor([elapsed], device='cuda', dtype=torch.float64)
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         elapsed = float(tt.item())
+    if args.dump_outputs and rank == 0:
+        r_, d_, _ = eng.reward_done()
+        dump_outputs(args.dump_outputs, {'obs': eng.obs(), 'reward': r_, 'done': d_, 'state': eng.state()})
     if rank == 0:
         achieved = n * EPMC_ALGO_BYTES_PER_ENV_STEP / (k_ms * 1e-3) / 1e9
         # how the engine ran a call of spl control steps (llenv.hip launch_epmc_step): ONE multi-step launch only with the rays fused and the grid at one wave per SIMD; otherwise
@@ -636,7 +675,7 @@ def main_epmc(args):
         kspl = spl if (spl > 1 and ray_mode < 2 and n <= 4096) else 1
         split = ray_mode >= (1 if spl == 1 else 2)
         traffic, issue, tsrc = committed_counters('epmc_step_kernel', n, kspl)
-        extra = {'cpu_baseline': cpu_baseline_env('epmc', epmc_env_config(args.element))} if (world == 1 and not args.no_cpu_baseline) else {}
+        extra = {'cpu_baseline': cpu_baseline_env('epmc', epmc_env_config(args.element))} if (args.full and world == 1 and not args.no_cpu_baseline) else {}
         print(json.dumps({**extra, 'build': build_record(), **{
             'metric': 'env-steps/sec (whole node), EPMC PlayGround env, random policy', 'value': world * n * args.steps / elapsed, 'unit': 'env-steps/s',
             'n_gpus': world, 'steps': args.steps, 'warmup': args.warmup, 'ms_per_step': elapsed / args.steps * 1e3, 'higher_is_better': True,
@@ -721,6 +760,9 @@ def main_sepmc(args):
         tt = torch.tensor([elapsed], device='cuda', dtype=torch.float64)
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         elapsed = float(tt.item())
+    if args.dump_outputs and rank == 0:
+        r_, d_, _ = eng.reward_done()
+        dump_outputs(args.dump_outputs, {'obs': eng.obs(), 'reward': r_, 'done': d_, 'state': eng.state()})
     if rank == 0:
         achieved = 2 * n_arenas * SEPMC_ALGO_BYTES_PER_ROBOT_STEP / (k_ms * 1e-3) / 1e9
         ray_mode = int(os.environ.get('LL_SPLIT_RAYS', '1'))          # (see main_epmc; this env's default leaves multi-step calls fused -- up to one wave per SIMD)
@@ -730,7 +772,7 @@ def main_sepmc(args):
         kspl = spl if (spl > 1 and ray_mode < 2 and (2 * n_arenas <= 4096 or one_wave)) else 1
         split = ray_mode >= (1 if spl == 1 else 2)
         traffic, issue, tsrc = committed_counters('sepmc_step_kernel', 2 * n_arenas, kspl)
-        extra = {'cpu_baseline': cpu_baseline_env('sepmc', sepmc_env_config())} if (world == 1 and not args.no_cpu_baseline) else {}
+        extra = {'cpu_baseline': cpu_baseline_env('sepmc', sepmc_env_config())} if (args.full and world == 1 and not args.no_cpu_baseline) else {}
         print(json.dumps({**extra, 'build': build_record(), **{
             'metric': 'robot-steps/sec (whole node), SEPMC chase-tag env, random policy', 'value': world * 2 * n_arenas * args.steps / elapsed, 'unit': 'robot-steps/s',
             'n_gpus': world, 'steps': args.steps, 'warmup': args.warmup, 'ms_per_step': elapsed / args.steps * 1e3, 'higher_is_better': True,

@@ -232,6 +232,71 @@ def _run_bench(extra_args, extra_env, timeout=900):
 
 
 ONE_DEVICE = {'LL_BENCH_BACKEND': 'gloo', 'LL_BENCH_ONE_DEVICE': '1'}
+ONE_RANK_PER_DEVICE = {'LL_BENCH_BACKEND': 'gloo'}
+ONE_DEVICE_RANKS = 3        # ranks that share device 0 in the one-GPU runs of the many-rank paths: with pytest and the launcher, at most 5 processes hold the GPU
+
+
+def eight_devices():
+    """The eight-rank runs put one rank on each of eight GPUs: eight rank processes sharing ONE device, plus pytest and the launcher, are more processes
+    than the machines this suite runs on let one GPU hold.  Checked before any rank starts; on one GPU the same paths run with ONE_DEVICE_RANKS ranks."""
+    torch = torch_cuda()
+    n = torch.cuda.device_count()
+    if n < 8:
+        pytest.skip('needs 8 GPUs (one rank per device), found %d' % n)
+
+
+def check_many_ranks(world, env, tag):
+    """`python bench.py --gpus <world>` -- the command starts its own ranks, 512 envs each, gather staged through gloo.  ONE line from rank 0, every
+    rank seen, every rank's gathered block equal to what its engine recorded, the learner's receive side 2 x world blocks; then the same hand-off as
+    world - 1 peer-to-peer pulls (--gather-mode p2p)."""
+    import os
+    steps, warm, n = 256, 128, 512
+    for mode in ('async', 'p2p'):
+        j, raw, root = _run_bench(['--gpus', world, '--steps', steps, '--warmup', warm, '--envs-per-gpu', n, '--gather-mode', mode], dict(env, LL_BENCH_VERIFY='1'), timeout=1500)
+        c = j['config']
+        assert j['n_gpus'] == world and j['steps'] == steps and j['scaling'] == 'weak'
+        assert abs(j['value'] - world * n * steps / (j['ms_per_step'] * 1e-3 * steps)) < 1e-6 * j['value']       # whole-job aggregate over the ranks
+        assert c['gather_check'] == 'ok' and c['unrolls_gathered'] == (steps + warm) // 128, c
+        g = c['gather']
+        assert g['mode'] == mode and g['receive_blocks'] == [2, world] and g['bytes_per_rank_per_unroll'] == n * 128 * 224 * 4
+        seen = g['ranks_seen']
+        assert [r['rank'] for r in seen] == list(range(world)) and len({r['pid'] for r in seen}) == world      # one process per rank
+        assert all(r['envs'] == n and r['control_steps'] == steps + warm and r['episodes'] > 0 for r in seen), seen
+        print(mode, 'stale re-seeds per rank (ranks sharing ONE device may start a launch while another rank holds some SIMDs):', [r['stale_reseeds'] for r in seen])
+        log_dir = os.path.join(root, 'gpurun_out', 'two_rank')
+        os.makedirs(log_dir, exist_ok=True)
+        with open(os.path.join(log_dir, 'bench_%s_%s.json' % (tag, mode)), 'w') as f:
+            f.write(raw + '\n')
+
+
+def check_one_rank_killed(world, kill, env, tag):
+    """The N > 1 failure path (round-5 review #6): `python bench.py --gpus <world>` with rank `kill` killed without a word after the warm-up (LL_BENCH_KILL_RANK
+    test hook: SIGKILL at the start of the timed phase).  The launch must end non-zero within the launcher's own patience, and ONE JSON error line must reach
+    stdout -- from whichever surviving rank noticed first -- naming its rank and the phase, instead of a bare time-out."""
+    import json
+    import os
+    import subprocess
+    import sys
+    import time
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY='0', LL_BENCH_KILL_RANK=str(kill), LL_BENCH_KILL_PHASE='timed', LL_BENCH_PG_TIMEOUT_S='60', LL_BENCH_STALL_S='90', **env)
+    for k in ('WORLD_SIZE', 'RANK', 'LOCAL_RANK', 'MASTER_PORT'):
+        env.pop(k, None)
+    t0 = time.time()
+    out = subprocess.run([sys.executable, os.path.join(root, 'bench.py'), '--gpus', str(world), '--steps', '256', '--warmup', '128', '--envs-per-gpu', '512'], env=env, cwd=root,
+                         capture_output=True, text=True, timeout=900)
+    took = time.time() - t0
+    lines = [json.loads(l) for l in out.stdout.splitlines() if l.startswith('{')]
+    assert out.returncode != 0, out.stdout[-2000:]
+    assert len(lines) == 1, (out.stdout[-3000:], out.stderr[-3000:])
+    j = lines[0]
+    assert 'error' in j and j['value'] is None and j['world'] == world and j['rank'] in range(world) and j['rank'] != kill, j
+    assert j['phase'] in ('timed', 'gather', 'warmup'), j                      # (a survivor is told while it is stepping or waiting in the barrier behind the warm-up)
+    print('killed rank %d -> error line from rank %d in phase %s after %.0f s: %s' % (kill, j['rank'], j['phase'], took, j['error'][:160]))
+    log_dir = os.path.join(root, 'gpurun_out', 'two_rank')
+    os.makedirs(log_dir, exist_ok=True)
+    with open(os.path.join(log_dir, 'bench_%s.json' % tag), 'w') as f:
+        f.write(out.stdout)
 
 
 def test_bench_two_ranks_on_one_device(tmp_path):
@@ -256,60 +321,29 @@ def test_bench_two_ranks_on_one_device(tmp_path):
 
 
 def test_bench_eight_ranks_on_one_device():
-    """BASELINE config 3's control flow at its real rank count (the driver's 8-GPU run cannot be rehearsed on a 1-GPU box): exactly
-    `python bench.py --gpus 8` -- the command starts its own eight ranks -- all on device 0, 512 envs each (8 x 128 single-wave workgroups: one per
-    SIMD, all resident together), gather staged through gloo.  ONE line from rank 0, eight ranks seen, every rank's gathered block equal to what
-    its engine recorded, the learner's receive side 2 x 8 blocks; then the same hand-off as seven peer-to-peer pulls (--gather-mode p2p)."""
-    import os
-    torch_cuda()
-    steps, warm, n = 256, 128, 512
-    for mode in ('async', 'p2p'):
-        j, raw, root = _run_bench(['--gpus', 8, '--steps', steps, '--warmup', warm, '--envs-per-gpu', n, '--gather-mode', mode], dict(ONE_DEVICE, LL_BENCH_VERIFY='1'), timeout=1500)
-        c = j['config']
-        assert j['n_gpus'] == 8 and j['steps'] == steps and j['scaling'] == 'weak'
-        assert abs(j['value'] - 8 * n * steps / (j['ms_per_step'] * 1e-3 * steps)) < 1e-6 * j['value']           # whole-job aggregate over the eight ranks
-        assert c['gather_check'] == 'ok' and c['unrolls_gathered'] == (steps + warm) // 128, c
-        g = c['gather']
-        assert g['mode'] == mode and g['receive_blocks'] == [2, 8] and g['bytes_per_rank_per_unroll'] == n * 128 * 224 * 4
-        seen = g['ranks_seen']
-        assert [r['rank'] for r in seen] == list(range(8)) and len({r['pid'] for r in seen}) == 8             # eight processes
-        assert all(r['envs'] == n and r['control_steps'] == steps + warm and r['episodes'] > 0 for r in seen), seen
-        print(mode, 'stale re-seeds per rank (ranks sharing ONE device may start a launch while another rank holds some SIMDs):', [r['stale_reseeds'] for r in seen])
-        log_dir = os.path.join(root, 'gpurun_out', 'two_rank')
-        os.makedirs(log_dir, exist_ok=True)
-        with open(os.path.join(log_dir, 'bench_eight_ranks_one_device_%s.json' % mode), 'w') as f:
-            f.write(raw + '\n')
+    """BASELINE config 3's control flow at its real rank count, exactly `python bench.py --gpus 8`: eight ranks, one per GPU (eight_devices: on a
+    one-GPU machine it skips, and test_bench_ranks_share_one_device runs the same checks with ONE_DEVICE_RANKS ranks on device 0)."""
+    eight_devices()
+    check_many_ranks(8, ONE_RANK_PER_DEVICE, 'eight_ranks_one_per_gpu')
 
 
 def test_bench_eight_ranks_one_rank_killed():
-    """The N > 1 failure path (round-5 review #6): `python bench.py --gpus 8` with rank 5 killed without a word after the warm-up (LL_BENCH_KILL_RANK test
-    hook: SIGKILL at the start of the timed phase).  The launch must end non-zero within the launcher's own patience, and ONE JSON error line must reach
-    stdout -- from whichever surviving rank noticed first -- naming its rank and the phase, instead of a bare time-out."""
-    import json
-    import os
-    import subprocess
-    import sys
-    import time
+    """The failure path at the real rank count: eight ranks, one per GPU, rank 5 killed (on one GPU: test_bench_rank_killed_ranks_share_one_device)."""
+    eight_devices()
+    check_one_rank_killed(8, 5, ONE_RANK_PER_DEVICE, 'eight_ranks_one_per_gpu_one_killed')
+
+
+def test_bench_ranks_share_one_device():
+    """The many-rank gather on ONE GPU: `python bench.py --gpus 3` -- three rank processes, all on device 0 (LL_BENCH_ONE_DEVICE), more than the two of
+    test_bench_two_ranks_on_one_device, so that rank 0 receives from several peers and pulls from several processes (p2p)."""
     torch_cuda()
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY='0', LL_BENCH_KILL_RANK='5', LL_BENCH_KILL_PHASE='timed', LL_BENCH_PG_TIMEOUT_S='60', LL_BENCH_STALL_S='90', **ONE_DEVICE)
-    for k in ('WORLD_SIZE', 'RANK', 'LOCAL_RANK', 'MASTER_PORT'):
-        env.pop(k, None)
-    t0 = time.time()
-    out = subprocess.run([sys.executable, os.path.join(root, 'bench.py'), '--gpus', '8', '--steps', '256', '--warmup', '128', '--envs-per-gpu', '512'], env=env, cwd=root,
-                         capture_output=True, text=True, timeout=900)
-    took = time.time() - t0
-    lines = [json.loads(l) for l in out.stdout.splitlines() if l.startswith('{')]
-    assert out.returncode != 0, out.stdout[-2000:]
-    assert len(lines) == 1, (out.stdout[-3000:], out.stderr[-3000:])
-    j = lines[0]
-    assert 'error' in j and j['value'] is None and j['world'] == 8 and j['rank'] in range(8) and j['rank'] != 5, j
-    assert j['phase'] in ('timed', 'gather', 'warmup'), j                      # (a survivor is told while it is stepping or waiting in the barrier behind the warm-up)
-    print('killed rank 5 -> error line from rank %d in phase %s after %.0f s: %s' % (j['rank'], j['phase'], took, j['error'][:160]))
-    log_dir = os.path.join(root, 'gpurun_out', 'two_rank')
-    os.makedirs(log_dir, exist_ok=True)
-    with open(os.path.join(log_dir, 'bench_eight_ranks_one_killed.json'), 'w') as f:
-        f.write(out.stdout)
+    check_many_ranks(ONE_DEVICE_RANKS, ONE_DEVICE, 'ranks_share_one_device')
+
+
+def test_bench_rank_killed_ranks_share_one_device():
+    """The killed-rank failure path on ONE GPU: three ranks on device 0, the middle one (rank 1) killed at the start of the timed phase."""
+    torch_cuda()
+    check_one_rank_killed(ONE_DEVICE_RANKS, 1, ONE_DEVICE, 'ranks_share_one_device_one_killed')
 
 
 def test_gather_overlaps_with_the_next_unroll():

@@ -12,7 +12,7 @@ import pytest
 
 from lifelike_agility_and_play_amd import urdf_model as um
 
-URDF = '/root/reference/src/lifelike/sim_envs/pybullet_envs/legged_robot/data/urdf/max.urdf'
+URDF = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'golden', 'max.urdf')     # the reference's legged_robot/data/urdf/max.urdf, stored as a fixture
 RX90 = um.rpy_to_mat([np.pi / 2, 0, 0])
 RY90 = um.rpy_to_mat([0, np.pi / 2, 0])
 
@@ -121,7 +121,6 @@ def test_composite_inertia_of_the_two_robots():
     assert (r < 1.0).all() and (r > 0.6).all()             # legs carry most of it by the parallel-axis terms, which do not change
 
 
-@pytest.mark.skipif(not os.path.exists(URDF), reason='the reference URDF lives only in the build container')
 def test_both_blobs_are_what_the_urdf_compiles_to():
     a, f = um.UrdfModel(URDF, 'collision_aabb'), um.UrdfModel(URDF, 'file')
     np.testing.assert_array_equal(a.blob(), um.model_blob('collision_aabb'))

@@ -26,15 +26,15 @@ case $TARGET in
     gpu_tests
     python tools/inertia_table.py --engine > $OUT/inertia_engine.md 2> $OUT/inertia_engine.err
     cat $OUT/inertia_engine.md; tail -3 $OUT/inertia_engine.err
-    python bench.py --no-cpu-baseline > $OUT/bench.log 2>$OUT/bench.err; tail -c 800 $OUT/bench.log ;;
+    python bench.py --full --no-cpu-baseline > $OUT/bench.log 2>$OUT/bench.err; tail -c 800 $OUT/bench.log ;;
   profile) tools/profile.sh $TAG ;;
   round2)        # second call of round 4: the suite at the new HEAD, what the register-budget builds disagree on, the p2p hand-off A/B
     gpu_tests -x
     python tools/diag_budgets.py > $OUT/diag_budgets.txt 2>&1; cat $OUT/diag_budgets.txt
     cp gpurun_out/two_rank/*.txt gpurun_out/two_rank/*.json $OUT/ 2>/dev/null; cat $OUT/p2p_no_cu.txt | head -8 ;;
   driver)
-    for i in 1 2 3; do LL_BENCH_TRIAD_FIRST=0 python bench.py --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline 2>/dev/null | show "driver-style, no triad first"; done
-    for i in 1 2 3; do python bench.py --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline 2>/dev/null | show "driver-style (triad first)  "; done
+    for i in 1 2 3; do LL_BENCH_TRIAD_FIRST=0 python bench.py --gpus 1 --steps 20 --warmup 5 --full --no-cpu-baseline 2>/dev/null | show "driver-style, no triad first"; done
+    for i in 1 2 3; do python bench.py --gpus 1 --steps 20 --warmup 5 --full --no-cpu-baseline 2>/dev/null | show "driver-style (triad first)  "; done
     python bench.py --gpus 1 --steps 2048 --warmup 256 --no-cpu-baseline 2>/dev/null | show "2048 steps                  " ;;
   round3)        # the whole suite (no -x), then what the ray families of the EPMC / SEPMC observation cost (ablation build, if it travelled)
     gpu_tests
@@ -107,10 +107,10 @@ case $TARGET in
     python tools/sweep.py "4096:4:10:10:32,65536:4:10:10:1" > $OUT/sweeps.txt 2>&1; python tools/sweep_epmc.py "4096:1:32,65536:1:1" >> $OUT/sweeps.txt 2>&1; python tools/sweep_sepmc.py "2048:0:32,32768:0:1" >> $OUT/sweeps.txt 2>&1; cat $OUT/sweeps.txt ;;
   r05h)          # the bars policy's fall histogram; driver-style lines with and without the triad in front; the EPMC / SEPMC bench lines with their CPU legs
     python tools/hole_fall_histogram.py 1024 600 > $OUT/hole_fall_histogram.txt 2>/dev/null; cat $OUT/hole_fall_histogram.txt
-    for i in 1 2 3; do LL_BENCH_TRIAD_FIRST=0 python bench.py --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline 2>/dev/null | tee -a $OUT/driver_style_raw.txt | show "driver-style, no triad first"; done > $OUT/driver_style.txt
-    for i in 1 2 3; do python bench.py --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline 2>/dev/null | tee -a $OUT/driver_style_raw.txt | show "driver-style (triad first)  "; done >> $OUT/driver_style.txt
+    for i in 1 2 3; do LL_BENCH_TRIAD_FIRST=0 python bench.py --gpus 1 --steps 20 --warmup 5 --full --no-cpu-baseline 2>/dev/null | tee -a $OUT/driver_style_raw.txt | show "driver-style, no triad first"; done > $OUT/driver_style.txt
+    for i in 1 2 3; do python bench.py --gpus 1 --steps 20 --warmup 5 --full --no-cpu-baseline 2>/dev/null | tee -a $OUT/driver_style_raw.txt | show "driver-style (triad first)  "; done >> $OUT/driver_style.txt
     python bench.py --gpus 1 --steps 2048 --warmup 256 --no-cpu-baseline 2>/dev/null | show "2048 steps                  " >> $OUT/driver_style.txt; cat $OUT/driver_style.txt
-    python bench.py --workload epmc > $OUT/epmc_bench.log 2>/dev/null; python bench.py --workload sepmc > $OUT/sepmc_bench.log 2>/dev/null; tail -c 300 $OUT/sepmc_bench.log ;;
+    python bench.py --workload epmc --full > $OUT/epmc_bench.log 2>/dev/null; python bench.py --workload sepmc --full > $OUT/sepmc_bench.log 2>/dev/null; tail -c 300 $OUT/sepmc_bench.log ;;
   pipe)          # A/B on one box: cone turns with the second select in the next turn's wait state (in-tree) against the round-4 turn (tools/_build/ab_nopipe.so); then parity
     for r in 1 2 3; do for v in "" tools/_build/ab_nopipe.so; do echo "== ${v:-in-tree (pipelined cone turns)} (round $r)"
       LL_LIB=$v python tools/sweep.py "4096:4:10:10:32,4096:4:10:10:1,65536:4:10:10:1"; LL_LIB=$v python tools/sweep_epmc.py "4096:1:32,65536:1:1"; LL_LIB=$v python tools/sweep_sepmc.py "2048:0:32,32768:0:1"; done; done > $OUT/cone_pipe_ab.txt 2>&1
@@ -165,7 +165,7 @@ PY
     grep "==\|steps/s" $OUT/ab.txt | cut -c1-150 ;;
   final)         # the round's closing call: the whole -m gpu suite at HEAD, then the three bench lines against the committed counters
     gpu_tests
-    python bench.py > $OUT/bench.log 2>$OUT/bench.err; tail -c 400 $OUT/bench.log
+    python bench.py --full > $OUT/bench.log 2>$OUT/bench.err; tail -c 400 $OUT/bench.log
     for W in epmc sepmc; do python bench.py --workload $W --no-cpu-baseline > $OUT/${W}_bench.log 2>$OUT/${W}_bench.err; tail -c 300 $OUT/${W}_bench.log; done
     python tools/sweep.py "4096:4:10:10:32,16384:4:10:10:32,65536:4:10:10:32,65536:4:10:10:1" > $OUT/sweep_tail.txt 2>&1; cat $OUT/sweep_tail.txt
     python tools/sweep_epmc.py "65536:1:1" >> $OUT/sweep_tail.txt 2>&1; python tools/sweep_sepmc.py "32768:0:1" >> $OUT/sweep_tail.txt 2>&1; tail -2 $OUT/sweep_tail.txt ;;

@@ -1,7 +1,7 @@
 #!/bin/bash
 # Everything profiles/ is built from, in one gpurun call:
 #   gpurun --timeout 900 -- 'tools/profile.sh r01'      then here:   python tools/profile_summarize.py r01
-# 1. bench.py as the driver runs it (with the CPU baseline)       -> gpurun_out/<tag>/bench.log
+# 1. bench.py --full (with the CPU baseline)                        -> <out>/<tag>/bench.log
 # 2. rocprofv3 --kernel-trace --stats of the same command          -> .../stats
 # 3. PMC passes, each on its own (no trace domains mixed in): SQ issue counters, FETCH_SIZE, WRITE_SIZE
 # 4. batch-size sweep and the per-wave timeline of the ablation build (if tools/_build/libllenv_abl.so travelled)
@@ -10,7 +10,7 @@ cd "$(dirname "$0")/.." || exit 1
 OUT=gpurun_out/$TAG
 mkdir -p $OUT
 export TMPDIR=/tmp
-python bench.py > $OUT/bench.log 2>$OUT/bench.err          # exactly what the driver runs at N = 1
+python bench.py --full > $OUT/bench.log 2>$OUT/bench.err          # the full line at N = 1: CPU baseline, one-launch-per-step leg, HBM triad
 B="python bench.py --gpus 1 --steps 320 --warmup 32 --no-cpu-baseline --no-single-step-leg"     # (multiples of the 32 control steps a launch runs)
 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -- $B > $OUT/bench_under_rocprof.log 2>&1
 S="python bench.py --gpus 1 --steps 96 --warmup 32 --no-cpu-baseline --no-single-step-leg"     # (three launches of 32 control steps: bench.py never times fewer than three)
@@ -30,7 +30,7 @@ if [ -f tools/_build/libllenv_abl.so ]; then
 fi
 # 5. the neighbours of the path: EPMC / SEPMC (bench line, kernel stats, the same PMC passes, sweeps) and the closed actor loop with the trained policy
 for W in epmc sepmc; do
-  python bench.py --workload $W ${LL_PROFILE_LEAN:+--no-cpu-baseline} > $OUT/${W}_bench.log 2>$OUT/${W}_bench.err      # the default run, CPU baseline leg included
+  python bench.py --workload $W --full ${LL_PROFILE_LEAN:+--no-cpu-baseline} > $OUT/${W}_bench.log 2>$OUT/${W}_bench.err      # the full run, CPU baseline leg included
   rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/${W}_stats -- python bench.py --workload $W --gpus 1 --steps 192 --warmup 32 --no-cpu-baseline > /dev/null 2>&1
   SW="python bench.py --workload $W --gpus 1 --steps 64 --warmup 32 --no-cpu-baseline"
   rocprofv3 --kernel-trace --output-format csv --pmc SQ_WAVES SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_WAIT_ANY SQ_ACTIVE_INST_ANY -d $OUT/${W}_pmc_sq -- $SW > /dev/null 2>&1
