@@ -1,0 +1,130 @@
+"""ctypes binding of include/hl/llenv_hl_policy.h: the trained EPMC / SEPMC policies as ONE fused kernel each inside libllenv.so,
+evaluated straight on an engine's device buffers, with each row's LSTM state kept on the device.  `oracle/epmc_policy.py` and
+`oracle/sepmc_policy.py` (NumPy, float64) state the same forward pass.
+
+    pol = HipEpmcPolicy('epmc_policy_hurdle.npz', max_rows=4096)
+    for t in range(T):
+        pol.act(engine)          # obs -> actions on the engine's stream; rows whose done flag is set start from zero state
+        engine.step()
+"""
+import ctypes as C
+import os
+
+import numpy as np
+
+from .. import capi
+
+LLH_EPMC, LLH_SEPMC = 1, 2
+N_FLOATS = {LLH_EPMC: 208437, LLH_SEPMC: 316806}
+OBS_DIM = {LLH_EPMC: 916, LLH_SEPMC: 965}
+ARRAYS = {LLH_EPMC: [0, 1] + list(range(47, 102)), LLH_SEPMC: [0, 1] + list(range(51, 152))}    # checkpoint array numbers, packing order
+
+_SIGS = {
+    'll_hl_policy_create': (C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p)]),
+    'll_hl_policy_destroy': (C.c_int, [C.c_void_p]),
+    'll_hl_policy_state_dim': (C.c_int, [C.c_void_p]),
+    'll_hl_policy_act': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
+    'll_hl_policy_reset_state': (C.c_int, [C.c_void_p, C.c_void_p]),
+    'll_hl_policy_get_state': (C.c_int, [C.c_void_p, C.c_void_p]),
+    'll_hl_policy_set_state': (C.c_int, [C.c_void_p, C.c_void_p]),
+    'll_hl_policy_enable_timing': (C.c_int, [C.c_void_p, C.c_int]),
+    'll_hl_policy_time_ms': (C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_int)]),
+}
+EXPORTED_SYMBOLS = sorted(_SIGS)
+_bound = {}
+
+
+def load_library(path=None):
+    lib = capi.load_library(path)
+    if id(lib) not in _bound:
+        for name, (res, args) in _SIGS.items():
+            fn = getattr(lib, name)
+            fn.restype, fn.argtypes = res, args
+        _bound[id(lib)] = True
+    return lib
+
+
+def pack_weights(kind, npz_path):
+    """The arrays of `kind` from an .npz with keys 'w<k>' (what tools/extract_epmc_policy.py writes), float32, flattened in checkpoint order."""
+    z = np.load(npz_path)
+    flat = np.concatenate([z['w%d' % k].astype(np.float32).ravel() for k in ARRAYS[kind]])
+    assert flat.size == N_FLOATS[kind], (flat.size, N_FLOATS[kind])
+    return np.ascontiguousarray(flat)
+
+
+def _vp(x):
+    return C.c_void_p(int(x)) if x else None
+
+
+class _HipHlPolicy(object):
+    KIND = None
+
+    def __init__(self, npz_path, max_rows, device=0, lib_path=None, weights=None):
+        self.lib = load_library(lib_path)
+        w = pack_weights(self.KIND, npz_path) if weights is None else np.ascontiguousarray(weights, dtype=np.float32)
+        self.max_rows = int(max_rows)
+        self._pid = os.getpid()
+        self.h = C.c_void_p()
+        self._chk(self.lib.ll_hl_policy_create(self.KIND, w.ctypes.data_as(C.c_void_p), int(w.size), self.max_rows, int(device), C.byref(self.h)))
+        self.state_dim = int(self.lib.ll_hl_policy_state_dim(self.h))
+
+    def _chk(self, rc):
+        if rc != 0:
+            raise capi.LLError(rc, self.lib.ll_last_error().decode())
+
+    def act_ptr(self, d_obs, d_actions, n_rows, stream=None, d_reset=None, d_code=None, d_heading=None, obs_stride=None):
+        """ll_hl_policy_act on raw device addresses; asynchronous on `stream` (None: the default stream)."""
+        self._chk(self.lib.ll_hl_policy_act(self.h, _vp(d_obs), int(OBS_DIM[self.KIND] if obs_stride is None else obs_stride), _vp(d_reset), _vp(d_actions),
+                                            _vp(d_code), _vp(d_heading), int(n_rows), _vp(stream)))
+
+    def act(self, engine, reset_from_done=True, d_code=None, d_heading=None):
+        """obs buffer of `engine` (an EpmcEngine / SepmcEngine, or a game holding one as .engine) -> its action buffer, queued on the engine's
+        stream.  reset_from_done: rows whose done flag is set (an auto-reset engine re-seeded them in the last step) start from zero state."""
+        eng = getattr(engine, 'engine', engine)
+        p = eng.device_ptrs()
+        self.act_ptr(p.obs, p.actions, p.n_envs, p.stream, p.done if reset_from_done else None, d_code, d_heading, p.obs_dim)
+
+    def reset_state(self, stream=None):
+        self._chk(self.lib.ll_hl_policy_reset_state(self.h, _vp(stream)))
+
+    def state(self):
+        """[max_rows][state_dim] float32 (EPMC: c | h; SEPMC: hlc c | hlc h | z c | z h)"""
+        s = np.empty((self.max_rows, self.state_dim), np.float32)
+        self._chk(self.lib.ll_hl_policy_get_state(self.h, s.ctypes.data_as(C.c_void_p)))
+        return s
+
+    def set_state(self, s):
+        s = np.ascontiguousarray(s, dtype=np.float32).reshape(self.max_rows, self.state_dim)
+        self._chk(self.lib.ll_hl_policy_set_state(self.h, s.ctypes.data_as(C.c_void_p)))
+
+    def enable_timing(self, on=True):
+        self._chk(self.lib.ll_hl_policy_enable_timing(self.h, 1 if on else 0))
+
+    def time_ms(self):
+        """(average ms per ll_hl_policy_act launch since the last call, number of launches)"""
+        ms, n = C.c_double(0), C.c_int(0)
+        self._chk(self.lib.ll_hl_policy_time_ms(self.h, C.byref(ms), C.byref(n)))
+        return ms.value, n.value
+
+    def close(self):
+        if getattr(self, 'h', None) is not None and self.h:
+            if getattr(self, '_pid', None) == os.getpid():      # (a fork()ed child inherits the object, not the HIP context: it must not destroy it)
+                self.lib.ll_hl_policy_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:     # noqa: BLE001
+            pass
+
+
+class HipEpmcPolicy(_HipHlPolicy):
+    """A trained environmental-level policy (tests/golden/epmc_policy_{hurdle,hole,cube}.npz layout); rows = the EPMC engine's envs."""
+    KIND = LLH_EPMC
+
+
+class HipSepmcPolicy(_HipHlPolicy):
+    """The trained strategic-level policy (tests/golden/sepmc_policy.npz layout); rows = 2 arena + robot, the SEPMC engine's row order.
+    d_heading (act / act_ptr) receives the high level's heading angle of every row."""
+    KIND = LLH_SEPMC
