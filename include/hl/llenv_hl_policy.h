@@ -46,6 +46,10 @@ extern "C" {
 #define LLH_EPMC_OBS_DIM 916   /* prop 99 | prop_a 36 | percep_2d 325 | percep_1d 128 | percep_front 325 | target 3 */
 #define LLH_SEPMC_OBS_DIM 965  /* ... percept_front | percept_vec 5 | oppo_info 15 | oppo_info_cheat 15 | flag_info 7 | flag_info_cheat 7 | with_flag 2 | control_spd 1 */
 #define LLH_ACT_DIM 12
+#define LLH_EPMC_VF_N_FLOATS 137872    /* arrays 2..46 of environmental_level_*.model: the value branch */
+#define LLH_SEPMC_VF_N_FLOATS 182864   /* arrays 2..50 of strategic_level.model */
+#define LLH_EPMC_N_HEADS 2             /* neglogp columns: z, llc */
+#define LLH_SEPMC_N_HEADS 3            /* hlc, z, llc */
 
 typedef struct ll_hl_policy ll_hl_policy;
 
@@ -65,11 +69,38 @@ int ll_hl_policy_state_dim(ll_hl_policy* p);
  */
 int ll_hl_policy_act(ll_hl_policy* p, const float* d_obs, int obs_stride, const uint8_t* d_reset, float* d_actions, int32_t* d_code,
                      float* d_heading, int n_rows, void* hip_stream);
-int ll_hl_policy_reset_state(ll_hl_policy* p, void* hip_stream);      /* every row to zero, queued on hip_stream */
+int ll_hl_policy_reset_state(ll_hl_policy* p, void* hip_stream);      /* every row to zero (the value state too, once attached), queued on hip_stream */
 /* host copies of the whole state buffer [max_rows][state_dim]; both wait for the device to be idle first */
 int ll_hl_policy_get_state(ll_hl_policy* p, float* h_state);
 int ll_hl_policy_set_state(ll_hl_policy* p, const float* h_state);
-/* HIP-event time of the ll_hl_policy_act launches since the last call (like ll_policy_time_ms) */
+/*
+ * The PPO actor (the self-fed heads of the training scripts' actor_type=PPO, use_value_head: True).
+ *
+ * ll_hl_policy_attach_value uploads the value branch, h_vf_weights = arrays 2..46 (EPMC, LLH_EPMC_VF_N_FLOATS) or 2..50 (SEPMC,
+ * LLH_SEPMC_VF_N_FLOATS) of the checkpoint in checkpoint order (tests/golden/epmc_value_*.npz, sepmc_value.npz), and gives every row a
+ * zeroed value LSTM state [max_rows][64] (c | h).  Attaching again replaces the weights and zeroes that state.
+ *
+ * ll_hl_policy_act_pg is ll_hl_policy_act with, for every row:
+ *   sample != 0  every head sampled with Philox4x32-10, key (seed lo, seed hi), counter (row * G + g, step lo, step hi, salt), one salt per head;
+ *                the draws depend on (seed, step, row) only:
+ *                  SEPMC heading  mu + exp(logstd) eps, mu = the clipped mean, the sample itself not clipped (G 1, one Box-Muller normal);
+ *                  z code         Gumbel-max argmax(logit - log(-log u)) over the 256 logits (G 64: word j of block g is code 4 g + j,
+ *                                 u = ((w >> 8) + 0.5) 2^-24), and the low-level controller runs at the sampled code;
+ *                  action         mean + exp(logstd) eps, twelve Box-Muller normals (G 3, as ll_policy_act_pg);
+ *   sample == 0  the modes: the argmax code, the mean action, the clipped mean heading (what ll_hl_policy_act emits).
+ *   d_neglogp    (nullable) [n_rows][n_heads] -log p of each emitted head, columns in action-space order: EPMC z, llc; SEPMC hlc, z, llc.
+ *                Categorical: logsumexp(logits) - logits[code]; Gaussian: 0.5 sum eps^2 + 0.5 d log(2 pi) + sum logstd.
+ *   d_value      (nullable) [n_rows] the value head; needs an attached branch (LL_EINVAL otherwise, before any launch).  The value state of
+ *                rows < n_rows advances on the calls that compute a value; d_reset zeroes it like the policy state.
+ * The policy state advances exactly as in ll_hl_policy_act.  The value branch runs as a second set of workgroups of the same launch.
+ */
+int ll_hl_policy_attach_value(ll_hl_policy* p, const float* h_vf_weights, int n_floats);
+int ll_hl_policy_act_pg(ll_hl_policy* p, const float* d_obs, int obs_stride, const uint8_t* d_reset, float* d_actions, int32_t* d_code, float* d_heading,
+                        float* d_neglogp, float* d_value, uint64_t seed, uint64_t step, int sample, int n_rows, void* hip_stream);
+/* host copies of the value state [max_rows][64] (c | h); LL_EINVAL without an attached branch; both wait for the device to be idle first */
+int ll_hl_policy_get_value_state(ll_hl_policy* p, float* h_state);
+int ll_hl_policy_set_value_state(ll_hl_policy* p, const float* h_state);
+/* HIP-event time of the ll_hl_policy_act and ll_hl_policy_act_pg launches since the last call (like ll_policy_time_ms) */
 int ll_hl_policy_enable_timing(ll_hl_policy* p, int on);
 int ll_hl_policy_time_ms(ll_hl_policy* p, double* avg_ms, int* n_launches);
 

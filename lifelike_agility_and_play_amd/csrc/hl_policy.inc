@@ -199,6 +199,40 @@ __device__ __forceinline__ float hl_lstm(const HlW& W, int k0, const float* x, f
   return h;
 }
 
+// PPO actor draws (ll_hl_policy_act_pg): key (seed lo, seed hi), counter (row * G + g, step lo, step hi, salt), one salt per head
+#define HL_HEADING_SALT 0x4EAD1Cu    // SEPMC heading: G 1, the first Box-Muller normal of the block
+#define HL_Z_SALT 0x2C0DE5u          // z code: G 64, word j of block g perturbs code 4 g + j
+#define HL_LLC_SALT 0x11C5A7u        // low-level action: G 3, four normals per block (as policy_noise)
+#define HL_LOG_2PI 1.8378770664093453f
+
+// four standard normals of one Philox block, formed as policy_noise (pmc_policy.inc) forms them
+__device__ __forceinline__ void hl_normals4(uint64_t seed, uint64_t step, uint32_t ctr, uint32_t salt, float* eps) {
+  uint32_t r[4];
+  philox4x32(ctr, (uint32_t)step, (uint32_t)(step >> 32), salt, (uint32_t)seed, (uint32_t)(seed >> 32), r);
+  const float k = 2.3283064365386963e-10f;   // 2^-32
+  const float u1 = fminf(((float)r[0] + 1.0f) * k, 1.0f), u2 = (float)r[1] * k, u3 = fminf(((float)r[2] + 1.0f) * k, 1.0f), u4 = (float)r[3] * k;
+  const float m1 = sqrtf(-2.0f * logf(u1)), m2 = sqrtf(-2.0f * logf(u3));
+  eps[0] = m1 * cosf(6.283185307179586f * u2); eps[1] = m1 * sinf(6.283185307179586f * u2);
+  eps[2] = m2 * cosf(6.283185307179586f * u4); eps[3] = m2 * sinf(6.283185307179586f * u4);
+}
+
+// Gumbel noise -log(-log u) of the 24-bit open-interval uniform u = ((w >> 8) + 0.5) 2^-24.  u is never rounded: below 1/2 it is exact in
+// float32 and -log u = -logf(u); above, 1 - u = ((2^24 - 1 - (w >> 8)) + 0.5) 2^-24 is exact and -log u = -log1pf(-(1 - u)).
+__device__ __forceinline__ float hl_gumbel(uint32_t w) {
+  const uint32_t k = w >> 8;
+  const float t = k < (1u << 23) ? -logf(((float)k + 0.5f) * 5.9604644775390625e-8f)
+                                 : -log1pf(-(((float)(0xFFFFFFu - k) + 0.5f) * 5.9604644775390625e-8f));
+  return -logf(t);
+}
+
+// what the PG launch hands the mid level: draws, the neglogp output and its column count, LDS for the z logits' logsumexp
+struct HlPg {
+  uint64_t seed, step;
+  int sample, nh;
+  float* neglogp;
+  float *pm, *ps;      // [16][16]: per-part max and sum of exp of the z logits
+};
+
 struct HlLds {
   float big[2 * 256 * POL_M];   // two activation buffers b0 | b1; the percept stacks' intermediate maps while those run
   float xs[136 * POL_M];        // normalised prop (135)
@@ -212,9 +246,11 @@ struct HlLds {
 
 // The mid level (EPMC's whole policy; SEPMC's mlc_encoder and llc) with the EPMC checkpoint's array numbers; the SEPMC arrays are OFF = 50
 // further on.  On entry: xs, and the target [3][16] in L.vin.  Writes actions / code of rows < n_rows.
-template <int OFF>
+// PG: the PPO actor's heads (HlPg): the code and the action sampled when g.sample, neglogp of both when g.neglogp.
+template <int OFF, bool PG = false>
 __device__ __forceinline__ void hl_mid(const HlW& W, HlLds& L, const float* __restrict__ obs, int stride, const uint8_t* __restrict__ reset, float* __restrict__ state,
-                                       int sdim, int soff, float* __restrict__ actions, int32_t* __restrict__ code_out, int row0, int n_rows, int wave, int lane, int tid) {
+                                       int sdim, int soff, float* __restrict__ actions, int32_t* __restrict__ code_out, int row0, int n_rows, int wave, int lane, int tid,
+                                       const HlPg& g = HlPg()) {
   float *b0 = L.big, *b1 = L.big + 256 * POL_M;
   hl_load_state(state, sdim, soff, reset, row0, n_rows, L.cs, L.hs, tid);
   hl_percepts(W, OFF + 49, obs, stride, row0, n_rows, L.big, L.feat, 32, tid);                     // usr_cmd_encoder: e2d | e1d | efr at 32..119
@@ -228,7 +264,30 @@ __device__ __forceinline__ void hl_mid(const HlW& W, HlLds& L, const float* __re
   hl_lstm(W, OFF + 79, b0, b1, L.cs, L.hs, state, sdim, soff, row0, n_rows, wave, lane, tid);
   pol_dense(L.hs, 32, W.a[OFF + 88], W.a[OFF + 89], 256, b0, 0, wave, lane);                     // z logits
   __syncthreads();
-  {   // first maximum over the 256 logits of each row (as in pmc_policy_kernel)
+  if constexpr (PG) {   // first maximum of logit (+ Gumbel noise when sampling) per row; max and sum of exp of 16 logits for the logsumexp
+    if (tid < 256) {
+      const int m = tid & 15, part = tid >> 4;
+      float mx = -3.0e38f, se = 0.0f, bv = -3.0e38f;
+      int bi = 0;
+      for (int q = 0; q < 16; q++) mx = fmaxf(mx, b0[(part * 16 + q) * POL_M + m]);
+      for (int blk = 0; blk < 4; blk++) {
+        uint32_t w[4] = {0u, 0u, 0u, 0u};
+        if (g.sample)
+          philox4x32((uint32_t)(row0 + m) * 64u + (uint32_t)(part * 4 + blk), (uint32_t)g.step, (uint32_t)(g.step >> 32), HL_Z_SALT, (uint32_t)g.seed,
+                     (uint32_t)(g.seed >> 32), w);
+#pragma unroll
+        for (int q = 0; q < 4; q++) {
+          const int c = part * 16 + blk * 4 + q;
+          const float v = b0[c * POL_M + m];
+          se += expf(v - mx);
+          const float pv = g.sample ? v + hl_gumbel(w[q]) : v;
+          if (pv > bv) { bv = pv; bi = c; }
+        }
+      }
+      L.pv[part * POL_M + m] = bv; L.pi[part * POL_M + m] = bi;
+      g.pm[part * POL_M + m] = mx; g.ps[part * POL_M + m] = se;
+    }
+  } else {   // first maximum over the 256 logits of each row (as in pmc_policy_kernel)
     const int m = tid & 15, part = (tid >> 4) & 15;
     float bv = -3.0e38f;
     int bi = 0;
@@ -247,6 +306,15 @@ __device__ __forceinline__ void hl_mid(const HlW& W, HlLds& L, const float* __re
       if (L.pv[p * POL_M + tid] > bv) { bv = L.pv[p * POL_M + tid]; bi = L.pi[p * POL_M + tid]; }
     L.best[tid] = bi;
     if (code_out && row0 + tid < n_rows) code_out[row0 + tid] = bi;
+    if constexpr (PG) {
+      if (g.neglogp && row0 + tid < n_rows) {                                                   // logsumexp(logits) - logits[code]
+        float mx = g.pm[tid];
+        for (int p = 1; p < 16; p++) mx = fmaxf(mx, g.pm[p * POL_M + tid]);
+        float se = 0.0f;
+        for (int p = 0; p < 16; p++) se += g.ps[p * POL_M + tid] * expf(g.pm[p * POL_M + tid] - mx);
+        g.neglogp[(long)(row0 + tid) * g.nh + g.nh - 2] = mx + logf(se) - b0[bi * POL_M + tid];
+      }
+    }
   }
   __syncthreads();
   for (int i = tid; i < 32 * POL_M; i += POL_THREADS) {                                          // zq = w90.T[code]: rows 96..127 of b1
@@ -263,9 +331,28 @@ __device__ __forceinline__ void hl_mid(const HlW& W, HlLds& L, const float* __re
   __syncthreads();
   pol_dense(b0, 256, W.a[OFF + 99], W.a[OFF + 100], 12, b1, 0, wave, lane);                      // mean action: rows 0..11 of b1
   __syncthreads();
-  for (int i = tid; i < POL_M * LLH_ACT_DIM; i += POL_THREADS) {
-    const int m = i / LLH_ACT_DIM, c = i - m * LLH_ACT_DIM;
-    if (row0 + m < n_rows) actions[(long)(row0 + m) * LLH_ACT_DIM + c] = b1[c * POL_M + m];
+  if constexpr (PG) {
+    if (tid < 64) {     // wavefront 0, lane = group * 16 + row: a = mean + exp(logstd) eps (logstd: array OFF + 101), neglogp summed over the groups
+      const int grp = lane >> 4, m = lane & 15, r = row0 + m;
+      float eps[4] = {0.0f, 0.0f, 0.0f, 0.0f}, nl = 0.0f;
+      if (grp < 3) {
+        if (g.sample) hl_normals4(g.seed, g.step, (uint32_t)r * 3u + (uint32_t)grp, HL_LLC_SALT, eps);
+#pragma unroll
+        for (int q = 0; q < 4; q++) {
+          const int c = 4 * grp + q;
+          const float ls = W.a[OFF + 101][c];
+          if (r < n_rows) actions[(long)r * LLH_ACT_DIM + c] = b1[c * POL_M + m] + expf(ls) * eps[q];
+          nl += 0.5f * eps[q] * eps[q] + ls;
+        }
+      }
+      nl += __shfl(nl, lane + 16) + __shfl(nl, lane + 32);
+      if (g.neglogp && grp == 0 && r < n_rows) g.neglogp[(long)r * g.nh + g.nh - 1] = nl + 0.5f * HL_LOG_2PI * LLH_ACT_DIM;
+    }
+  } else {
+    for (int i = tid; i < POL_M * LLH_ACT_DIM; i += POL_THREADS) {
+      const int m = i / LLH_ACT_DIM, c = i - m * LLH_ACT_DIM;
+      if (row0 + m < n_rows) actions[(long)(row0 + m) * LLH_ACT_DIM + c] = b1[c * POL_M + m];
+    }
   }
 }
 
@@ -319,9 +406,150 @@ __global__ __launch_bounds__(POL_THREADS) void hl_policy_kernel(HlW W, const flo
   }
 }
 
+// The value branch's view of the policy kernel's LDS (a union with HlLds in the PG launch): a 512-row and a 256-row activation buffer.
+struct HlVLds {
+  float a[512 * POL_M];         // the percept stacks' intermediate maps, then the dense layers' outputs; the LSTM's scratch
+  float b[256 * POL_M];         // percept features (rows 0..119), normalised prop (rows 120..255); then the LSTM input
+  float cs[32 * POL_M], hs[32 * POL_M];
+  float vin[32 * POL_M];        // EPMC: target (3); SEPMC: percept_vec | oppo_info_cheat | flag_info_cheat | with_flag (29)
+};
+
+struct HlPgLds {
+  union {
+    HlLds P;
+    HlVLds V;
+  } u;
+  float pm[16 * POL_M], ps[16 * POL_M];
+};
+
+// The value branch (epmc_net.py:226-244, sepmc_net.py:271-292) of 16 rows on the checkpoint's arrays 2..46 (EPMC) / 2..50 (SEPMC); its LSTM
+// state [max_rows][64] (c | h) in vstate, zeroed by reset like the policy's.  value[r] <- the value of rows r < n_rows.
+template <int KIND>
+__device__ __forceinline__ void hl_value(const HlW& W, HlVLds& V, const float* __restrict__ obs, int stride, const uint8_t* __restrict__ reset,
+                                         float* __restrict__ vstate, float* __restrict__ value, int row0, int n_rows, int wave, int lane, int tid) {
+  float *a = V.a, *b = V.b, *xs = V.b + 120 * POL_M;
+  for (int i = tid; i < POL_M * 135; i += POL_THREADS) {        // the policy's rms normalisation (arrays 0, 1)
+    const int m = i / 135, k = i - m * 135, r = row0 + m;
+    const float x = r < n_rows ? obs[(long)r * stride + k] : 0.0f;
+    xs[k * POL_M + m] = fminf(fmaxf((x - W.a[0][k]) / (W.a[1][k] + 1e-8f), -5.0f), 5.0f);
+  }
+  if (KIND == LLH_EPMC) {
+    if (tid < 3 * POL_M) {                                       // target (913..915)
+      const int k = tid >> 4, m = tid & 15, r = row0 + m;
+      V.vin[k * POL_M + m] = r < n_rows ? obs[(long)r * stride + 913 + k] : 0.0f;
+    }
+  } else if (tid < 29 * POL_M) {                                 // percept_vec 913..917 | oppo_info_cheat 933..947 | flag_info_cheat 955..961 | with_flag 962..963
+    const int k = tid >> 4, m = tid & 15, r = row0 + m;
+    const int col = k < 5 ? 913 + k : (k < 20 ? 933 + k - 5 : (k < 27 ? 955 + k - 20 : 962 + k - 27));
+    V.vin[k * POL_M + m] = r < n_rows ? obs[(long)r * stride + col] : 0.0f;
+  }
+  hl_load_state(vstate, 64, 0, reset, row0, n_rows, V.cs, V.hs, tid);
+  __syncthreads();
+  float h;
+  int kv;
+  if (KIND == LLH_EPMC) {
+    hl_percepts(W, 4, obs, stride, row0, n_rows, a, b, 32, tid);                     // usr_cmd_encoder: e2d | e1d | efr -> b rows 32..119
+    pol_dense(V.vin, 3, W.a[28], W.a[29], 32, b, 1, wave, lane);                     //                  vec -> b rows 0..31
+    pol_dense(xs, 135, W.a[2], W.a[3], 128, a + 128 * POL_M, 2, wave, lane);         // fc1, tanh -> a rows 128..255
+    __syncthreads();
+    pol_dense(b, 120, W.a[30], W.a[31], 64, a, 1, wave, lane);                       // bottleneck -> a rows 0..63
+    __syncthreads();
+    pol_dense(a, 64, W.a[32], W.a[33], 128, a + 256 * POL_M, 2, wave, lane);         // fc2, tanh -> a rows 256..383
+    __syncthreads();
+    pol_dense(a + 128 * POL_M, 256, W.a[34], W.a[35], 256, b, 2, wave, lane);        // fc3 of [fc1 | fc2], tanh -> b
+    __syncthreads();
+    h = hl_lstm(W, 36, b, a, V.cs, V.hs, vstate, 64, 0, row0, n_rows, wave, lane, tid);
+    kv = 45;
+  } else {
+    hl_percepts(W, 4, obs, stride, row0, n_rows, a, b, 0, tid);                      // mlc_usr_cmd_encoder: e2d | e1d | efr -> b rows 0..87
+    pol_dense(b, 88, W.a[28], W.a[29], 64, a, 1, wave, lane);                        // bottleneck -> a rows 0..63
+    pol_dense(V.vin, 29, W.a[32], W.a[33], 64, a + 64 * POL_M, 1, (wave + 4) & 7, lane);   // hlc_usr_cmd_encoder 1 -> a rows 64..127
+    pol_dense(xs, 135, W.a[2], W.a[3], 128, a + 128 * POL_M, 2, wave, lane);         // fc1, tanh -> a rows 128..255
+    __syncthreads();
+    pol_dense(a, 64, W.a[30], W.a[31], 128, a + 256 * POL_M, 2, wave, lane);         // fc2, tanh -> a rows 256..383
+    pol_dense(a + 64 * POL_M, 64, W.a[34], W.a[35], 64, b, 1, (wave + 4) & 7, lane); // hlc_usr_cmd_encoder 2 -> b rows 0..63
+    __syncthreads();
+    pol_dense(b, 64, W.a[36], W.a[37], 128, a + 384 * POL_M, 2, wave, lane);         // fc3, tanh -> a rows 384..511
+    __syncthreads();
+    pol_dense(a + 128 * POL_M, 384, W.a[38], W.a[39], 256, b, 2, wave, lane);        // fc4 of [fc1 | fc2 | fc3], tanh -> b
+    __syncthreads();
+    h = hl_lstm(W, 40, b, a, V.cs, V.hs, vstate, 64, 0, row0, n_rows, wave, lane, tid);
+    kv = 49;
+  }
+  const int m = tid >> 5, j = tid & 31, r = row0 + m;
+  const float v = hl_sum32(h * W.a[kv][j]) + W.a[kv + 1][0];                         // value dense, linear
+  if (j == 0 && r < n_rows) value[r] = v;
+}
+
+// The PPO actor launch: blockIdx.y 0 = the policy of hl_policy_kernel with its heads sampled / scored (HlPg); blockIdx.y 1 (launched only
+// when a value is asked for) = the value branch of the same rows.  Neither waits on the other.
+template <int KIND>
+__global__ __launch_bounds__(POL_THREADS) void hl_policy_pg_kernel(HlW W, const float* __restrict__ obs, int stride, const uint8_t* __restrict__ reset,
+                                                                   float* __restrict__ state, float* __restrict__ vstate, float* __restrict__ actions,
+                                                                   int32_t* __restrict__ code_out, float* __restrict__ heading_out, float* __restrict__ neglogp,
+                                                                   float* __restrict__ value, uint64_t seed, uint64_t step, int sample, int n_rows) {
+  __shared__ HlPgLds S;
+  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, row0 = blockIdx.x * POL_M;
+  if (blockIdx.y == 1) {
+    hl_value<KIND>(W, S.u.V, obs, stride, reset, vstate, value, row0, n_rows, wave, lane, tid);
+    return;
+  }
+  HlLds& L = S.u.P;
+  HlPg g;
+  g.seed = seed; g.step = step; g.sample = sample; g.neglogp = neglogp; g.pm = S.pm; g.ps = S.ps;
+  g.nh = KIND == LLH_EPMC ? LLH_EPMC_N_HEADS : LLH_SEPMC_N_HEADS;
+  for (int i = tid; i < POL_M * 135; i += POL_THREADS) {        // rms normalisation + clip to +-5 (layers.py:55)
+    const int m = i / 135, k = i - m * 135, r = row0 + m;
+    const float x = r < n_rows ? obs[(long)r * stride + k] : 0.0f;
+    L.xs[k * POL_M + m] = fminf(fmaxf((x - W.a[0][k]) / (W.a[1][k] + 1e-8f), -5.0f), 5.0f);
+  }
+  if (KIND == LLH_EPMC) {
+    if (tid < 3 * POL_M) {                                       // target (913..915)
+      const int k = tid >> 4, m = tid & 15, r = row0 + m;
+      L.vin[k * POL_M + m] = r < n_rows ? obs[(long)r * stride + 913 + k] : 0.0f;
+    }
+    __syncthreads();
+    hl_mid<0, true>(W, L, obs, stride, reset, state, 64, 0, actions, code_out, row0, n_rows, wave, lane, tid, g);
+  } else {
+    float *b0 = L.big, *b1 = L.big + 256 * POL_M;
+    if (tid < 29 * POL_M) {                                      // percept_vec 913..917 | oppo_info 918..932 | flag_info 948..954 | with_flag 962..963
+      const int k = tid >> 4, m = tid & 15, r = row0 + m;
+      const int col = k < 20 ? 913 + k : (k < 27 ? 948 + k - 20 : 962 + k - 27);
+      L.vin[k * POL_M + m] = r < n_rows ? obs[(long)r * stride + col] : 0.0f;
+    }
+    hl_load_state(state, 128, 0, reset, row0, n_rows, L.cs, L.hs, tid);
+    __syncthreads();
+    hl_percepts(W, 53, obs, stride, row0, n_rows, L.big, L.feat, 0, tid);
+    pol_dense(L.xs, 135, W.a[51], W.a[52], 64, b1, 1, wave, lane);
+    pol_dense(L.feat, 88, W.a[77], W.a[78], 64, b1 + 64 * POL_M, 1, (wave + 4) & 7, lane);
+    pol_dense(L.vin, 29, W.a[79], W.a[80], 64, b0, 1, wave, lane);
+    __syncthreads();
+    pol_dense(b0, 64, W.a[81], W.a[82], 64, b1 + 128 * POL_M, 1, (wave + 4) & 7, lane);
+    __syncthreads();
+    pol_dense(b1, 192, W.a[83], W.a[84], 256, b0, 1, wave, lane);
+    __syncthreads();
+    const float h = hl_lstm(W, 85, b0, b1, L.cs, L.hs, state, 128, 0, row0, n_rows, wave, lane, tid);
+    const int m = tid >> 5, j = tid & 31, r = row0 + m;
+    const float mu = fminf(fmaxf(hl_sum32(h * W.a[94][j]) + W.a[95][0], -HL_PI), HL_PI);   // the Gaussian head's mean, clipped to +-pi
+    if (j == 0) {   // heading = mu + exp(a96) eps, not clipped (a96, 'logvar' in sepmc_net.py, is the DiagGaussian's logstd half); the mid level's target
+      float eps[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+      if (sample) hl_normals4(seed, step, (uint32_t)r, HL_HEADING_SALT, eps);
+      const float ls = W.a[96][0], hd = mu + expf(ls) * eps[0];
+      L.vin[0 * POL_M + m] = cosf(hd);
+      L.vin[1 * POL_M + m] = sinf(hd);
+      L.vin[2 * POL_M + m] = r < n_rows ? obs[(long)r * stride + 964] : 0.0f;
+      if (heading_out && r < n_rows) heading_out[r] = hd;
+      if (neglogp && r < n_rows) neglogp[(long)r * LLH_SEPMC_N_HEADS] = 0.5f * eps[0] * eps[0] + 0.5f * HL_LOG_2PI + ls;
+    }
+    __syncthreads();
+    hl_mid<50, true>(W, L, obs, stride, reset, state, 128, 64, actions, code_out, row0, n_rows, wave, lane, tid, g);
+  }
+}
+
 struct ll_hl_policy {
   int kind, device, max_rows, state_dim;
   float *d_w, *d_state;
+  float *d_vw, *d_vstate;        // the value branch (ll_hl_policy_attach_value) and its state [max_rows][64]; null until attached
   HlW W;
   bool timing;
   std::vector<std::pair<hipEvent_t, hipEvent_t>> evs;
@@ -334,6 +562,12 @@ static const int HL_MID_SIZES[55] = {8640, 64, 4, 4, 256, 4, 64, 4, 16, 1, 16, 4
                                      24576, 256, 65536, 256, 3072, 12, 12};
 static const int HL_HLC_SIZES[46] = {8640, 64, 4, 4, 256, 4, 64, 4, 16, 1, 16, 4, 64, 4, 64, 4, 16, 1, 4, 4, 256, 4, 64, 4, 16, 1,
                                      5632, 64, 1856, 64, 4096, 64, 49152, 256, 32768, 4096, 128, 128, 128, 128, 128, 32, 32, 32, 1, 1};
+
+// array sizes of the value branches: EPMC 2..46, SEPMC 2..50
+static const int HL_VF_EPMC_SIZES[45] = {17280, 128, 4, 4, 256, 4, 64, 4, 16, 1, 16, 4, 64, 4, 64, 4, 16, 1, 4, 4, 256, 4, 64, 4, 16, 1, 96, 32, 7680, 64,
+                                         8192, 128, 65536, 256, 32768, 4096, 128, 128, 128, 128, 128, 32, 32, 32, 1};
+static const int HL_VF_SEPMC_SIZES[49] = {17280, 128, 4, 4, 256, 4, 64, 4, 16, 1, 16, 4, 64, 4, 64, 4, 16, 1, 4, 4, 256, 4, 64, 4, 16, 1, 5632, 64, 8192,
+                                          128, 1856, 64, 4096, 64, 8192, 128, 98304, 256, 32768, 4096, 128, 128, 128, 128, 128, 32, 32, 32, 1};
 
 static void hl_check(ll_hl_policy* p) {
   if (!p) throw PmcError(LL_EINVAL, "null policy");
@@ -366,7 +600,7 @@ int ll_hl_policy_create(int kind, const float* h_weights, int n_floats, int max_
   if (tot != (size_t)want) throw PmcError(LL_EINVAL, "internal: array size table");
   ll_hl_policy* p = new ll_hl_policy();
   p->kind = kind; p->device = device; p->max_rows = max_rows; p->state_dim = kind == LLH_EPMC ? 64 : 128;
-  p->timing = false; p->ev_used = 0; p->d_w = nullptr; p->d_state = nullptr;
+  p->timing = false; p->ev_used = 0; p->d_w = nullptr; p->d_state = nullptr; p->d_vw = nullptr; p->d_vstate = nullptr;
   const size_t sbytes = (size_t)max_rows * p->state_dim * sizeof(float);
   if (hipMalloc(&p->d_w, ((size_t)want + 256) * sizeof(float)) != hipSuccess || hipMalloc(&p->d_state, sbytes) != hipSuccess) {
     if (p->d_w) (void)hipFree(p->d_w);
@@ -398,6 +632,8 @@ int ll_hl_policy_destroy(ll_hl_policy* p) {
     for (auto& e : p->evs) { (void)hipEventDestroy(e.first); (void)hipEventDestroy(e.second); }
     (void)hipFree(p->d_w);
     (void)hipFree(p->d_state);
+    if (p->d_vw) (void)hipFree(p->d_vw);
+    if (p->d_vstate) (void)hipFree(p->d_vstate);
     delete p;
   }
   LL_CATCH
@@ -407,6 +643,24 @@ int ll_hl_policy_state_dim(ll_hl_policy* p) {
   if (!p) return LL_EINVAL;
   return p->state_dim;
 }
+
+}  // extern "C"
+
+// the start event of a timed launch (null when timing is off or un-polled timing has stopped recording)
+static std::pair<hipEvent_t, hipEvent_t>* hl_timing_begin(ll_hl_policy* p, hipStream_t st) {
+  if (!p->timing || p->ev_used >= 16384) return nullptr;
+  if (p->ev_used == p->evs.size()) {
+    hipEvent_t a, b;
+    HIPCHK(hipEventCreate(&a));
+    HIPCHK(hipEventCreate(&b));
+    p->evs.push_back(std::make_pair(a, b));
+  }
+  std::pair<hipEvent_t, hipEvent_t>* ev = &p->evs[p->ev_used++];
+  HIPCHK(hipEventRecord(ev->first, st));
+  return ev;
+}
+
+extern "C" {
 
 int ll_hl_policy_act(ll_hl_policy* p, const float* d_obs, int obs_stride, const uint8_t* d_reset, float* d_actions, int32_t* d_code, float* d_heading,
                      int n_rows, void* hip_stream) {
@@ -418,17 +672,7 @@ int ll_hl_policy_act(ll_hl_policy* p, const float* d_obs, int obs_stride, const 
   LL_CHECK(!d_heading || p->kind == LLH_SEPMC, "d_heading: the EPMC policy has no heading");
   HIPCHK(hipSetDevice(p->device));
   hipStream_t st = (hipStream_t)hip_stream;
-  std::pair<hipEvent_t, hipEvent_t>* ev = nullptr;
-  if (p->timing && p->ev_used < 16384) {          // un-polled timing stops recording instead of growing without bound
-    if (p->ev_used == p->evs.size()) {
-      hipEvent_t a, b;
-      HIPCHK(hipEventCreate(&a));
-      HIPCHK(hipEventCreate(&b));
-      p->evs.push_back(std::make_pair(a, b));
-    }
-    ev = &p->evs[p->ev_used++];
-    HIPCHK(hipEventRecord(ev->first, st));
-  }
+  std::pair<hipEvent_t, hipEvent_t>* ev = hl_timing_begin(p, st);     // un-polled timing stops recording instead of growing without bound
   const dim3 grid((n_rows + POL_M - 1) / POL_M), block(POL_THREADS);
   if (p->kind == LLH_EPMC)
     hipLaunchKernelGGL(hl_policy_kernel<LLH_EPMC>, grid, block, 0, st, p->W, d_obs, obs_stride, d_reset, p->d_state, d_actions, d_code, d_heading, n_rows);
@@ -444,8 +688,86 @@ int ll_hl_policy_reset_state(ll_hl_policy* p, void* hip_stream) {
   hl_check(p);
   HIPCHK(hipSetDevice(p->device));
   HIPCHK(hipMemsetAsync(p->d_state, 0, (size_t)p->max_rows * p->state_dim * sizeof(float), (hipStream_t)hip_stream));
+  if (p->d_vstate) HIPCHK(hipMemsetAsync(p->d_vstate, 0, (size_t)p->max_rows * 64 * sizeof(float), (hipStream_t)hip_stream));
   LL_CATCH
 }
+
+int ll_hl_policy_attach_value(ll_hl_policy* p, const float* h_vf_weights, int n_floats) {
+  LL_TRY
+  hl_check(p);
+  LL_CHECK(h_vf_weights, "null argument");
+  const bool ep = p->kind == LLH_EPMC;
+  const int want = ep ? LLH_EPMC_VF_N_FLOATS : LLH_SEPMC_VF_N_FLOATS, n_arr = ep ? 45 : 49;
+  const int* sizes = ep ? HL_VF_EPMC_SIZES : HL_VF_SEPMC_SIZES;
+  if (n_floats != want)
+    throw PmcError(LL_EINVAL, ep ? "value weights: expected arrays 2..46 of an EPMC checkpoint (137872 floats)"
+                                 : "value weights: expected arrays 2..50 of the SEPMC checkpoint (182864 floats)");
+  size_t tot = 0;
+  for (int i = 0; i < n_arr; i++) tot += (size_t)sizes[i];
+  if (tot != (size_t)want) throw PmcError(LL_EINVAL, "internal: value array size table");
+  HIPCHK(hipSetDevice(p->device));
+  HIPCHK(hipDeviceSynchronize());                 // a launch in flight may still read the branch being replaced
+  if (!p->d_vw) {
+    const size_t sbytes = (size_t)p->max_rows * 64 * sizeof(float);
+    if (hipMalloc(&p->d_vw, (size_t)want * sizeof(float)) != hipSuccess) { p->d_vw = nullptr; throw PmcError(LL_ENOMEM, "hipMalloc failed"); }
+    if (hipMalloc(&p->d_vstate, sbytes) != hipSuccess) {
+      (void)hipFree(p->d_vw);
+      p->d_vw = nullptr; p->d_vstate = nullptr;
+      throw PmcError(LL_ENOMEM, "hipMalloc failed");
+    }
+  }
+  HIPCHK(hipMemcpy(p->d_vw, h_vf_weights, (size_t)want * sizeof(float), hipMemcpyHostToDevice));
+  HIPCHK(hipMemset(p->d_vstate, 0, (size_t)p->max_rows * 64 * sizeof(float)));
+  HIPCHK(hipDeviceSynchronize());
+  size_t off = 0;
+  for (int i = 0; i < n_arr; i++) { p->W.a[2 + i] = p->d_vw + off; off += (size_t)sizes[i]; }
+  LL_CATCH
+}
+
+int ll_hl_policy_act_pg(ll_hl_policy* p, const float* d_obs, int obs_stride, const uint8_t* d_reset, float* d_actions, int32_t* d_code, float* d_heading,
+                        float* d_neglogp, float* d_value, uint64_t seed, uint64_t step, int sample, int n_rows, void* hip_stream) {
+  LL_TRY
+  hl_check(p);
+  LL_CHECK(d_obs && d_actions, "null argument");
+  LL_CHECK(n_rows > 0 && n_rows <= p->max_rows, "n_rows must be 1 .. max_rows");
+  LL_CHECK(obs_stride == (p->kind == LLH_EPMC ? LLH_EPMC_OBS_DIM : LLH_SEPMC_OBS_DIM), "obs_stride is not the policy's obs dim (916 EPMC, 965 SEPMC)");
+  LL_CHECK(!d_heading || p->kind == LLH_SEPMC, "d_heading: the EPMC policy has no heading");
+  LL_CHECK(!d_value || p->d_vw, "d_value: no value branch attached (ll_hl_policy_attach_value)");
+  HIPCHK(hipSetDevice(p->device));
+  hipStream_t st = (hipStream_t)hip_stream;
+  std::pair<hipEvent_t, hipEvent_t>* ev = hl_timing_begin(p, st);
+  const dim3 grid((n_rows + POL_M - 1) / POL_M, d_value ? 2 : 1), block(POL_THREADS);
+  if (p->kind == LLH_EPMC)
+    hipLaunchKernelGGL(hl_policy_pg_kernel<LLH_EPMC>, grid, block, 0, st, p->W, d_obs, obs_stride, d_reset, p->d_state, p->d_vstate, d_actions, d_code, d_heading,
+                       d_neglogp, d_value, seed, step, sample, n_rows);
+  else
+    hipLaunchKernelGGL(hl_policy_pg_kernel<LLH_SEPMC>, grid, block, 0, st, p->W, d_obs, obs_stride, d_reset, p->d_state, p->d_vstate, d_actions, d_code, d_heading,
+                       d_neglogp, d_value, seed, step, sample, n_rows);
+  HIPCHK(hipGetLastError());
+  if (ev) HIPCHK(hipEventRecord(ev->second, st));
+  LL_CATCH
+}
+
+// host <-> the value state [max_rows][64]
+static int hl_value_state_copy(ll_hl_policy* p, void* h_state, bool to_host) {
+  LL_TRY
+  hl_check(p);
+  LL_CHECK(h_state, "null argument");
+  LL_CHECK(p->d_vstate, "no value branch attached (ll_hl_policy_attach_value)");
+  HIPCHK(hipSetDevice(p->device));
+  HIPCHK(hipDeviceSynchronize());
+  const size_t bytes = (size_t)p->max_rows * 64 * sizeof(float);
+  if (to_host)
+    HIPCHK(hipMemcpy(h_state, p->d_vstate, bytes, hipMemcpyDeviceToHost));
+  else
+    HIPCHK(hipMemcpy(p->d_vstate, h_state, bytes, hipMemcpyHostToDevice));
+  HIPCHK(hipDeviceSynchronize());
+  LL_CATCH
+}
+
+int ll_hl_policy_get_value_state(ll_hl_policy* p, float* h_state) { return hl_value_state_copy(p, h_state, true); }
+
+int ll_hl_policy_set_value_state(ll_hl_policy* p, const float* h_state) { return hl_value_state_copy(p, const_cast<float*>(h_state), false); }
 
 int ll_hl_policy_get_state(ll_hl_policy* p, float* h_state) {
   LL_TRY
