@@ -130,6 +130,7 @@ struct EpmcEngine {
   }
   void step(const float* d_act) {
     if (!have_reset) throw PmcError(LL_ESTATE, "ll_epmc_reset must be called before ll_epmc_step");
+    base.need_launchable(LL_ENGINE_EPMC);
     StepParams Q = base.P;
     Q.actions = d_act ? d_act : base.d_actions;
     EpmcParams R = E;
@@ -146,6 +147,7 @@ struct EpmcEngine {
   // episode, draw counter), so nothing but the actions' Philox step index moves from step to step
   void step_random_n(float sigma, int n_steps) {
     if (!have_reset) throw PmcError(LL_ESTATE, "ll_epmc_reset must be called before ll_epmc_step_random_n");
+    base.need_launchable(LL_ENGINE_EPMC);
     if (!(sigma > 0.0f) || n_steps <= 0) throw PmcError(LL_EINVAL, "sigma and n_steps must be positive");
     if (pending_step_draws != 0) throw PmcError(LL_ESTATE, "scripted draws apply to single steps only");
     StepParams Q = base.P;
@@ -155,6 +157,7 @@ struct EpmcEngine {
   }
   void step_scripted(const float* h_actions, const float* h_state, const uint8_t* h_hit, const float* h_frac, const float* h_draws, int n_draws) {
     if (!have_reset) throw PmcError(LL_ESTATE, "ll_epmc_reset must be called before ll_epmc_step_scripted");
+    base.need_launchable(LL_ENGINE_EPMC);
     const size_t N = base.P.n_envs;
     ensure_script_buffers(n_draws);
     base.bk.sync();

@@ -491,6 +491,9 @@ struct HipBackend {
   bool co_resident(const StepParams& P) const {
     const int blocks = (P.n_envs + PMC_ENVS_PER_WAVE - 1) / PMC_ENVS_PER_WAVE;
     if (deterministic) return false;
+    // the XROWS builds run multi-step calls in one launch only within one wave per SIMD: beyond it they run as single launches (the 256-register
+    // multi-step XROWS build once returned near-3e38 entries for one env of 4352 where single launches were finite; it is not built)
+    if (pmc_launch_xrows(P, LL_ENGINE_PMC) && blocks > simds) return false;
     return blocks <= simds || blocks <= 2 * simds_hw;
   }
   void set_stream(void* s) { stream = s ? (hipStream_t)s : own; }
@@ -547,8 +550,7 @@ struct HipBackend {
     EpmcParams E = E_in;
     E.split_rays = split ? 1 : 0;
 #define LL_GO(KERNEL, PARAMS) hipLaunchKernelGGL(KERNEL, dim3(blocks), dim3(PMC_WAVE), lds_bytes_epmc(), stream, PARAMS, E)
-    if (pmc_wants_xrows_terrain(P)) {                    // the extended contact rows (round 6): the cone builds with XROWS, every step a launch of its own
-      if (!cone) throw PmcError(LL_EINVAL, "self_friction / leg_edges need friction_mode 2 (the extended contact rows exist in the cone builds)");
+    if (pmc_launch_xrows(P, LL_ENGINE_EPMC)) {          // the extended contact rows (round 6): the cone builds with XROWS, every step a launch of its own (EpmcEngine refused the pyramid)
       StepParams Q = P;
       Q.n_steps = 1;
       for (int sl = 0; sl < P.n_steps; sl++, Q.step_count++) {
@@ -590,8 +592,7 @@ struct HipBackend {
     SepmcParams S = S_in;
     S.e.split_rays = split ? 1 : 0;
 #define LL_GO(KERNEL, PARAMS) hipLaunchKernelGGL(KERNEL, dim3(blocks), dim3(PMC_WAVE), lds_bytes_epmc(), stream, PARAMS, S)
-    if (pmc_wants_xrows_terrain(P)) {                    // the extended contact rows (round 6): see launch_epmc_step
-      if (!cone) throw PmcError(LL_EINVAL, "self_friction / pair_friction / max_pair / leg_edges need friction_mode 2 (the extended contact rows exist in the cone builds)");
+    if (pmc_launch_xrows(P, LL_ENGINE_SEPMC)) {         // the extended contact rows (round 6): see launch_epmc_step
       StepParams Q = P;
       Q.n_steps = 1;
       for (int sl = 0; sl < P.n_steps; sl++, Q.step_count++) {
@@ -629,12 +630,10 @@ struct HipBackend {
     const int blocks = (P.n_envs + PMC_ENVS_PER_WAVE - 1) / PMC_ENVS_PER_WAVE;
     std::pair<hipEvent_t, hipEvent_t>* ev = timing_begin(P.n_steps);
     const bool one = blocks <= simds, multi = P.n_steps > 1;
-    if (pmc_wants_xrows(P)) {                            // the extended contact rows (round 6): flat-ground cone builds with XROWS
-      if (P.friction_mode != 2 || P.set_obstacle) throw PmcError(LL_EINVAL, "self_friction needs friction_mode 2 and no jump obstacle (the extended contact rows exist in the flat-ground cone builds)");
+    if (pmc_launch_xrows(P, LL_ENGINE_PMC)) {           // the extended contact rows (round 6): flat-ground cone builds with XROWS (PmcEngine refused the pyramid and the obstacle)
       if (one) { if (multi) hipLaunchKernelGGL((pmc_step_kernel<1, false, true, true, true>), dim3(blocks), dim3(PMC_WAVE), lds_bytes(), stream, P);
                  else       hipLaunchKernelGGL((pmc_step_kernel<1, false, false, true, true>), dim3(blocks), dim3(PMC_WAVE), lds_bytes(), stream, P); }
-      else     { if (multi) hipLaunchKernelGGL((pmc_step_kernel<2, false, true, true, true>), dim3(blocks), dim3(PMC_WAVE), lds_bytes_epmc(), stream, P);
-                 else       hipLaunchKernelGGL((pmc_step_kernel<2, false, false, true, true>), dim3(blocks), dim3(PMC_WAVE), lds_bytes_epmc(), stream, P); }
+      else       hipLaunchKernelGGL((pmc_step_kernel<2, false, false, true, true>), dim3(blocks), dim3(PMC_WAVE), lds_bytes_epmc(), stream, P);    // (single steps only: co_resident)
     } else
     if (P.set_obstacle && P.friction_mode == 2) {
       if (one) { if (multi) hipLaunchKernelGGL((pmc_step_kernel<1, true, true, true>), dim3(blocks), dim3(PMC_WAVE), lds_bytes_epmc(), stream, P);

@@ -146,6 +146,11 @@ struct PmcEngine {
     if (reset && !have_reset) throw PmcError(LL_ESTATE, "ll_reset must be called before ll_step");
     if (reset && P.set_obstacle && !have_obstacles) throw PmcError(LL_ESTATE, "set_obstacle needs ll_load_obstacles");
   }
+  // the spec switches as set must have a build of `engine` that honours them (pmc_launch_refusal): checked before a step touches anything
+  void need_launchable(int engine) const {
+    const std::string e = pmc_launch_refusal(P, engine);
+    if (!e.empty()) throw PmcError(LL_EINVAL, e);
+  }
 
   // PLE:150-171
   void reset(const int32_t* env_ids, int n, const int32_t* clip, const double* t0) {
@@ -189,6 +194,7 @@ struct PmcEngine {
   // Philox stream as fill_random_actions(), so step_random(s) == fill_random_actions(s); step(nullptr).
   void step(const float* d_act, float sigma = 0.0f, int n_steps = 1) {
     need(true, true);
+    need_launchable(LL_ENGINE_PMC);
     // A launch runs at most LL_MAX_STEPS_PER_LAUNCH control steps (the per-step slots of the sampling table), and a multi-step launch whose grid
     // the chip cannot hold at once runs as single launches: its waves could not wait for each other's finished episodes (bk.co_resident)
     const int per = (n_steps > 1 && !bk.co_resident(P)) ? 1 : LL_MAX_STEPS_PER_LAUNCH;
@@ -234,6 +240,7 @@ struct PmcEngine {
   float *d_script_state = nullptr, *d_script_feet = nullptr;
   void step_scripted(const float* d_act, const float* h_state, const float* h_feet) {
     need(true, true);
+    need_launchable(LL_ENGINE_PMC);
     const size_t N = P.n_envs;
     if (!d_script_state) { d_script_state = dalloc<float>(N * 37); d_script_feet = dalloc<float>(N * 24); }
     bk.sync();

@@ -304,12 +304,12 @@ inline std::string pmc_set_spec_param(StepParams& P, int id, double v) {
     case LLM_SPEC_MAX_DEPEN_SPEED: P.max_depen = (float)v; break;
     case LLM_SPEC_LINK_DAMPING: P.link_damping = (float)v; break;
     case LLM_SPEC_MAX_CONTACTS_PER_LEG:
-      if (!(v >= 1 && v <= LLM_MAX_CONTACTS_PER_LEG)) return "max contacts per leg must be 1..4";
+      if (!(v >= 1 && v <= LLM_MAX_CONTACTS_PER_LEG && v == floor(v))) return "max_contacts_per_leg must be an integer 1..4";
       P.max_contacts = (int)v; break;
     case LLM_SPEC_SELF_COLLISION: P.self_collision = v > 0.5 ? 1.0f : 0.0f; break;
     case LLM_SPEC_SELF_MARGIN: P.self_margin = (float)v; break;
     case LLM_SPEC_MAX_SELF:
-      if (!(v >= 0 && v <= LLM_MAX_SELF)) return "self-collision rows per robot must be 0..2";
+      if (!(v >= 0 && v <= LLM_MAX_SELF && v == floor(v))) return "max_self (self-collision rows per robot) must be an integer 0..2";
       P.max_self = (int)v; break;
     case LLM_SPEC_ERP: P.erp = (float)v; pmc_resolve_erps(P); break;
     case LLM_SPEC_LIMIT_ERP: P.spec_limit_erp = (float)v; pmc_resolve_erps(P); break;
@@ -327,7 +327,7 @@ inline std::string pmc_set_spec_param(StepParams& P, int id, double v) {
       if (!(v >= 0.0 && v <= 4.0)) return "pair_friction must be in [0, 4]";
       P.pair_friction = (float)v; break;
     case LLM_SPEC_MAX_PAIR:
-      if (!(v >= 0 && v <= LLM_MAX_PAIR_CAP)) return "robot-robot rows per pair must be 0..4";
+      if (!(v >= 0 && v <= LLM_MAX_PAIR_CAP && v == floor(v))) return "max_pair (robot-robot rows per pair) must be an integer 0..4";   // (the oracle rounds: on integers the two agree)
       P.max_pair = (int)v; break;
     case LLM_SPEC_LEG_EDGES:
       if (!(v == 0.0 || v == 1.0)) return "leg_edges must be 0 or 1";
@@ -357,6 +357,39 @@ inline std::string pmc_set_spec_param(StepParams& P, int id, double v) {
     default: return "unknown spec parameter id";
   }
   return "";
+}
+// The engine a step launch serves: the XROWS builds and what they can carry differ between the three.
+enum { LL_ENGINE_PMC = 0, LL_ENGINE_EPMC = 1, LL_ENGINE_SEPMC = 2 };
+// Does a launch of `engine` need its XROWS build?  Only for the switches that have rows there: leg-leg friction in every engine, the terrain edges across
+// leg boxes where there is terrain (EPMC, SEPMC; PMC on flat ground has no edges, and with the jump obstacle it is refused below), the robot-robot rows in
+// SEPMC alone.  The launches (llenv.hip HipBackend, tests/emul) pick their build by this; pmc_wants_xrows stays what device code reads (Pmc::substep).
+inline bool pmc_launch_xrows(const StepParams& P, int engine) {
+  if (engine == LL_ENGINE_PMC) return P.self_friction > 0.0f;
+  if (engine == LL_ENGINE_EPMC) return P.self_friction > 0.0f || P.leg_edges != 0;
+  return pmc_wants_xrows_terrain(P);
+}
+// Can a step of `engine` honour the switches as they are set?  "" or the refusal, naming the switch.  Every backend shares it: the engines call it before
+// anything of the step is consumed, recorded (kernel timing) or launched, so a refused step leaves the engine as it was.
+inline std::string pmc_launch_refusal(const StepParams& P, int engine) {
+  if (engine == LL_ENGINE_PMC && P.set_obstacle) {
+    if (P.self_friction > 0.0f) return "self_friction is not built with the jump obstacle (the leg-leg friction rows exist in the flat-ground cone builds)";
+    if (P.leg_edges != 0) return "leg_edges is not built with the jump obstacle (no PMC build carries the obstacle's edges across the leg boxes)";
+  }
+  // the oracle finds the jump obstacle's hits (prim_hits_box) and the robot-robot contacts and terrain touches of a chase-tag arena (find_pair_contacts,
+  // touch_classes) within the constant LLM_CONTACT_MARGIN; the engine would apply the switch there too
+  if (P.margin_dist != (float)LLM_CONTACT_MARGIN && (engine == LL_ENGINE_SEPMC || (engine == LL_ENGINE_PMC && P.set_obstacle)))
+    return engine == LL_ENGINE_SEPMC ? "contact_margin is not built for the chase-tag arena (its robot-robot contacts and touch flags keep LLM_CONTACT_MARGIN)"
+                                     : "contact_margin is not built with the jump obstacle (its hit test keeps LLM_CONTACT_MARGIN)";
+  // the pyramid build with the jump obstacle leaves the oracle's bars by 2e-3 under a moved limit ERP (tests/spec_matrix.py): not held, not offered
+  if (engine == LL_ENGINE_PMC && P.set_obstacle && P.friction_mode != 2 && P.spec_limit_erp != (float)LLM_LIMIT_ERP)
+    return "limit_erp is not held to the oracle with the jump obstacle under friction_mode 0 (use friction_mode 2)";
+  if (P.friction_mode == 2 || !pmc_launch_xrows(P, engine)) return "";
+  std::string who;
+  if (P.self_friction > 0.0f) who += " / self_friction";
+  if (engine == LL_ENGINE_SEPMC && P.pair_friction > 0.0f) who += " / pair_friction";
+  if (engine == LL_ENGINE_SEPMC && P.max_pair != LLM_MAX_PAIR) who += " / max_pair";
+  if (engine != LL_ENGINE_PMC && P.leg_edges != 0) who += " / leg_edges";
+  return who.substr(3) + " needs friction_mode 2 (the extended contact rows exist in the cone builds)";
 }
 inline double pmc_get_spec_param(const StepParams& P, int id) {
   switch (id) {

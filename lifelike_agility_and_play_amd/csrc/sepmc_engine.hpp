@@ -133,6 +133,7 @@ struct SepmcEngine {
   }
   void step(const float* d_act) {
     if (!have_reset) throw PmcError(LL_ESTATE, "ll_sepmc_reset must be called before ll_sepmc_step");
+    base.need_launchable(LL_ENGINE_SEPMC);
     StepParams Q = base.P;
     Q.actions = d_act ? d_act : base.d_actions;
     SepmcParams R = S;
@@ -148,6 +149,7 @@ struct SepmcEngine {
   // episode, draw counter), so nothing but the actions' Philox step index moves from step to step
   void step_random_n(float sigma, int n_steps) {
     if (!have_reset) throw PmcError(LL_ESTATE, "ll_sepmc_reset must be called before ll_sepmc_step_random_n");
+    base.need_launchable(LL_ENGINE_SEPMC);
     if (!(sigma > 0.0f) || n_steps <= 0) throw PmcError(LL_EINVAL, "sigma and n_steps must be positive");
     if (pending_step_draws != 0) throw PmcError(LL_ESTATE, "scripted draws apply to single steps only");
     StepParams Q = base.P;
@@ -158,6 +160,7 @@ struct SepmcEngine {
   void step_scripted(const float* h_actions, const float* h_state, const uint8_t* h_hit, const float* h_frac, const uint8_t* h_vis, const int32_t* h_contacts,
                      const float* h_draws, int n_draws) {
     if (!have_reset) throw PmcError(LL_ESTATE, "ll_sepmc_reset must be called before ll_sepmc_step_scripted");
+    base.need_launchable(LL_ENGINE_SEPMC);
     const size_t N = base.P.n_envs, A = N / 2;
     ensure_script_buffers(n_draws);
     base.bk.sync();

@@ -47,10 +47,7 @@ struct HostBackend {
           if (P.set_obstacle) Pmc<HostLanesPipe>::step_env<true, true>(lq, P, env, act, sl);
           else Pmc<HostLanesPipe>::step_env<false, true>(lq, P, env, act, sl);
         }
-        else if (P.friction_mode == 2 && pmc_wants_xrows(P)) {                   // the extended contact rows (llenv.hip launch_step): the XROWS build
-          if (P.set_obstacle) K::step_env<true, true, true>(ln, P, env, act, sl);
-          else K::step_env<false, true, true>(ln, P, env, act, sl);
-        }
+        else if (pmc_launch_xrows(P, LL_ENGINE_PMC)) K::step_env<false, true, true>(ln, P, env, act, sl);   // the extended contact rows (llenv.hip launch_step): the XROWS build
         else if (P.set_obstacle && P.friction_mode == 2) K::step_env<true, true>(ln, P, env, act, sl);
         else if (P.set_obstacle) K::step_env<true>(ln, P, env, act, sl);
         else if (P.friction_mode == 2) K::step_env<false, true>(ln, P, env, act, sl);
@@ -123,7 +120,7 @@ struct HostBackend {
         for (int j = 0; j < 3; j++) act[j] = ln.ldl(P.actions, (long)env * 12 + j, 3);
         const bool park = getenv("LL_EMUL_PARK") != nullptr, cone = P.friction_mode == 2;      // park: the larger-batch GPU build's variant (tests)
         if (park) { if (cone) { HostLanesLds lq(P.candc); Epmc<HostLanesLds>::step_env<true, true>(lq, P, E, env, act); } else Epmc<HostLanes>::step_env<true>(ln, P, E, env, act); }
-        else if (cone && pmc_wants_xrows_terrain(P)) Epmc<HostLanes>::step_env<false, true, true>(ln, P, E, env, act);
+        else if (pmc_launch_xrows(P, LL_ENGINE_EPMC)) Epmc<HostLanes>::step_env<false, true, true>(ln, P, E, env, act);
         else      { if (cone) Epmc<HostLanes>::step_env<false, true>(ln, P, E, env, act); else Epmc<HostLanes>::step_env(ln, P, E, env, act); }
         if (E.split_rays) Epmc<HostLanes>::percept_row_host(P, E, env);
       }
@@ -166,7 +163,7 @@ struct HostBackend {
           fN act[3];
           for (int j = 0; j < 3; j++) act[j] = ln.ldl(P.actions, (long)row * 12 + j, 3);
           if (park) Sepmc<HostLanes>::step_env<true>(ln, P, S, row, act);
-          else if (cone && pmc_wants_xrows_terrain(P)) Sepmc<HostLanes>::step_env<false, true, true>(ln, P, S, row, act);
+          else if (pmc_launch_xrows(P, LL_ENGINE_SEPMC)) Sepmc<HostLanes>::step_env<false, true, true>(ln, P, S, row, act);
           else if (cone) Sepmc<HostLanes>::step_env<false, true>(ln, P, S, row, act);
           else Sepmc<HostLanes>::step_env(ln, P, S, row, act);
         });
