@@ -707,5 +707,6 @@ typedef SepmcEngine<HipBackend> SEPMC_ENGINE;
 #include "sepmc_capi.inc"
 #include "pmc_policy.inc"
 #include "hl_policy.inc"
+#include "hl_unroll.inc"
 #include "xfer_capi.inc"
 #endif  // LL_KERNELS_ONLY
