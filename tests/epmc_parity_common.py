@@ -54,7 +54,54 @@ class spec_variant:
         orc.reset_spec(); orc.set_spec(**BASE_SPEC)
 
 
+BASE_CFG = {}          # env_config fields every engine and every oracle call of this module (and of sepmc_parity_common) runs under: cfg_variant()
+
+
+class cfg_variant:
+    """with cfg_variant(control_freq=25.0, kd=1.0): ... -- the checks of this module (and of sepmc_parity_common) at another point of the env_config:
+    the fields are merged into every env_config dict an engine or an oracle env is made from (`friction_range` into its env_randomize_config,
+    `solver_iterations` handed to make_*_config), and the restated control steps of the oracle take kp, kd, max_tau and the substep count from them."""
+
+    def __init__(self, **cfg):
+        self.cfg = cfg
+
+    def __enter__(self):
+        self.saved = dict(BASE_CFG)
+        BASE_CFG.update(self.cfg)
+
+    def __exit__(self, *a):
+        BASE_CFG.clear(); BASE_CFG.update(self.saved)
+
+
+def with_base_cfg(cfg_dict):
+    """`cfg_dict` with the fields of the current cfg_variant merged in (a copy)"""
+    import copy
+    d = copy.deepcopy(cfg_dict)
+    for k, v in BASE_CFG.items():
+        if k == 'friction_range':
+            d['env_randomize_config']['friction_range'] = list(v)
+        else:
+            d[k] = copy.deepcopy(v)
+    return d
+
+
+def pd_scalars():
+    """kp, kd, max_tau and the substeps of one control step (PGE:86, CTG:57; sim_freq is fixed at 500) under the current cfg_variant; the defaults are
+    those of env_config(): 50, 0.5, 16, ten substeps"""
+    return (float(BASE_CFG.get('kp', 50.0)), float(BASE_CFG.get('kd', 0.5)), float(BASE_CFG.get('max_tau', 16.0)),
+            int((1.0 / float(BASE_CFG.get('control_freq', 50.0))) / epmc_capi.TIME_STEP))
+
+
+def oracle_kw():
+    """make_oracle_batch arguments of the scratch batch the restated control steps run on"""
+    kp, kd, max_tau, _ = pd_scalars()
+    return dict(control_freq=float(BASE_CFG.get('control_freq', 50.0)), kp=kp, kd=kd, max_tau=max_tau, solver_iterations=int(BASE_CFG.get('solver_iterations', 10)))
+
+
 def make_engine(cfg_dict, n_envs, lib_path, **kw):
+    cfg_dict = with_base_cfg(cfg_dict)
+    if 'solver_iterations' in cfg_dict:
+        kw.setdefault('solver_iterations', cfg_dict.pop('solver_iterations'))
     cfg = epmc_capi.make_epmc_config(n_envs, cfg_dict, **kw)
     E = epmc_capi.EpmcEngine(cfg, urdf_model.default_model_blob(), lib_path=lib_path)
     E.set_spec(**BASE_SPEC)
@@ -485,15 +532,16 @@ def statics_to_records(rows):
 
 
 def oracle_control_step(B, orc, s0, act, push_trace, mu, near, r32=False, **spec):
-    """Ten substeps of the oracle from state s0 with the PD target of one action (what one engine step does); r32 rounds the state to float32
+    """The substeps (ten at 50 Hz) of the oracle from state s0 with the PD target of one action (what one engine step does); r32 rounds the state to float32
     between substeps.  Returns the end state and how close the deepest-K picks came to their discontinuity (oracle.selection_margin)."""
     orc.reset_spec()
     orc.set_spec(**{**BASE_SPEC, **spec})
     s = s0.copy()
     tgt = np.clip(s[13:25] + np.asarray(act, np.float64), -3.0, 3.0)
     sel = np.inf
-    for k in range(10):
-        tau = np.clip(50.0 * (tgt - s[13:25]) - 0.5 * s[25:37], -16.0, 16.0)
+    kp, kd, max_tau, n_sub = pd_scalars()
+    for k in range(n_sub):
+        tau = np.clip(kp * (tgt - s[13:25]) - kd * s[25:37], -max_tau, max_tau)
         push = push_trace[k, 1:4] if push_trace[k, 0] > 0.5 else None
         B.selection_margin()
         s = B.substep_terrain(s, tau, mu, near, 0.5 / 0.9, push)[0]
@@ -608,7 +656,7 @@ def check_terrain_physics_against_oracle(lib_path, n_envs=16, seed=11, total_env
         E.step_host(act)
         es = E.state().astype(np.float64)
         tr = E.push_trace().astype(np.float64)
-        B = make_oracle_batch(orc, urdf_model.default_model_blob(), mocap.load_mocap('', 0.02), n_envs=1, kd=0.5, max_tau=16.0)
+        B = make_oracle_batch(orc, urdf_model.default_model_blob(), mocap.load_mocap('', 0.02), n_envs=1, **oracle_kw())
         for k, i in enumerate(idx):
             rec = recs_all[k]
             p = st32[i, 0:3]
@@ -674,7 +722,7 @@ def check_trunk_on_edges_against_oracle(lib_path, n_envs=16, seed=5, cap_ill=Non
         E.step_host(act)
         es = E.state().astype(np.float64)
         tr = E.push_trace().astype(np.float64)
-        B = make_oracle_batch(orc, blob, mocap.load_mocap('', 0.02), n_envs=1, kd=0.5, max_tau=16.0)
+        B = make_oracle_batch(orc, blob, mocap.load_mocap('', 0.02), n_envs=1, **oracle_kw())
         for i in range(n_envs):
             rec = recs_all[i]
             p = st32[i, 0:3]
@@ -748,7 +796,7 @@ def _check_legs_on_edges_against_oracle(lib_path, n_envs, seed, total_envs, cap_
     E.step_host(act)
     es = E.state().astype(np.float64)
     tr = E.push_trace().astype(np.float64)
-    B = make_oracle_batch(orc, blob, mocap.load_mocap('', 0.02), n_envs=1, kd=0.5, max_tau=16.0)
+    B = make_oracle_batch(orc, blob, mocap.load_mocap('', 0.02), n_envs=1, **oracle_kw())
     for k, i in enumerate(idx):
         rec = recs_all[k]
         p = st32[i, 0:3]
@@ -773,9 +821,10 @@ def check_free_running_against_oracle_env(lib_path, n_steps=4, elements=(1, 3, 0
     blob, table, init = urdf_model.default_model_blob(), mocap.load_mocap('', 0.02), epmc_capi.default_init_state()
     worst = dict(state=0.0, percep_same=1.0, reward=0.0)
     for element in elements:
-        cfg = env_config(element, aux=aux, obs_rand=obs_rand, cmd_range=(3, 5))
+        cfg = with_base_cfg(env_config(element, aux=aux, obs_rand=obs_rand, cmd_range=(3, 5)))
         cfg['env_randomize_config']['disturb_force_config'] = {'start_time': 0.0, 'interval_time': 1.0, 'duration_time': 0.5, 'horizontal_force': [10, 50], 'vertical_force': [0, 10]}
         n = 3
+        P3 = 3 * sum({'joint_pos': 12, 'joint_vel': 12, 'root_lin_vel_loc': 3, 'root_ang_vel_loc': 3, 'e_g': 3}[k] for k in cfg['prop_type']) + 36   # prop | prop_a: 135 with the five keys
         E = make_engine(cfg, n, lib_path, seed=1)
         runs = [FR.EpmcFreeRun(cfg, blob, table, init, seed=0) for _ in range(n)]
         U = np.full((n, epmc_capi.LLE_MAX_DRAWS), 0.5, np.float32)
@@ -797,11 +846,12 @@ def check_free_running_against_oracle_env(lib_path, n_steps=4, elements=(1, 3, 0
                 err = np.abs(quat_align(st_e[i], r.env.state) - r.env.state)
                 worst['state'] = max(worst['state'], err[:7].max() / tol)
                 assert err[:7].max() < tol and err[13:25].max() < 5 * tol, (element, i, t, err[:7].max(), err[13:25].max())
-                pe, po = obs_e[i][135:913], np.asarray(obs_o[i])[135:913]
+                assert obs_e[i].shape == np.asarray(obs_o[i]).shape
+                pe, po = obs_e[i][P3:P3 + 778], np.asarray(obs_o[i])[P3:P3 + 778]
                 same = np.abs(pe - po) < 2e-3 + 20 * tol
                 worst['percep_same'] = min(worst['percep_same'], same.mean())
                 assert same.mean() > 0.97, (element, i, t, same.mean())      # a ray grazing a box edge may fall either side
-                np.testing.assert_allclose(obs_e[i][913:916], np.asarray(obs_o[i])[913:916], atol=2e-3 + 20 * tol)
+                np.testing.assert_allclose(obs_e[i][P3 + 778:P3 + 781], np.asarray(obs_o[i])[P3 + 778:P3 + 781], atol=2e-3 + 20 * tol)
             if rew_o is not None:
                 rew_e, done_e, _ = E.reward_done()
                 for i in range(n):

@@ -5,7 +5,9 @@ modules stand in for them.  Only the reference's own code
 computes the expected values; the stubs merely hold state.  The fake BulletClient
 cannot step physics: a scripted list of dynamic-robot states is injected instead
 (one per control step), and foot positions returned by ``getLinkStates`` are
-scripted inputs too.  Outputs -> tests/golden/pmc_golden.npz (inputs + expected).
+scripted inputs too.  Outputs -> tests/golden/pmc_golden.npz (inputs + expected) at the training scripts' config,
+and tests/golden/pmc_golden_cfg2.npz: a second, smaller pass at the factory's own defaults
+(25 Hz, kd 1.0, PLE's reward weights) with a permuted subset prop_type.
 
     python tests/golden/gen_golden.py
 """
@@ -74,7 +76,8 @@ class FakeBulletClient(object):
 
     def __init__(self, connection_mode=None):
         self.bodies = []
-        self.script = []            # scripted dyn states (37,) consumed one per 10 stepSimulation calls
+        self.script = []            # scripted dyn states (37,) consumed one per n_sub stepSimulation calls (one control step)
+        self.n_sub = 10
         self.n_sim = 0
         self.feet = {0: np.zeros((4, 3)), 1: np.zeros((4, 3))}     # scripted getLinkStates positions
 
@@ -122,7 +125,7 @@ class FakeBulletClient(object):
 
     def stepSimulation(self):
         self.n_sim += 1
-        if self.n_sim % 10 == 0 and self.script:
+        if self.n_sim % self.n_sub == 0 and self.script:
             s = self.script.pop(0)
             set_dyn(self, s)
 
@@ -163,6 +166,117 @@ PMC_CONFIG = dict(                                                   # test_prim
     prop_type=['joint_pos', 'joint_vel', 'root_ang_vel_loc', 'root_lin_vel_loc', 'e_g'],
     prioritized_sample_factor=3.0, set_obstacle=False, obstacle_height=0.2, kp=50.0, kd=0.5, max_tau=18,
     reward_weights={'joint_pos': 0.3, 'joint_vel': 0.05, 'end_effector': 0.1, 'root_pose': 0.5, 'root_vel': 0.05})
+
+
+# the factory's defaults (create_pybullet_envs.py:28-59: control_freq 25, kd 1.0, reward_weights None -> PLE:359-363, uniform sampling) with a
+# permuted subset of the proprioception keys; nothing else is set
+CFG2 = dict(arena_id='LeggedRobotTracking', data_path=MOCAP_DIR, prop_type=['e_g', 'joint_vel', 'joint_pos'])
+CFG2_DEFAULTS = dict(control_freq=25.0, sim_freq=500.0, kp=50.0, kd=1.0, max_tau=18.0, prioritized_sample_factor=0.0)      # what the factory fills in
+
+
+def second_config(create_tracking_game, MotionLib, LeggedRobot, names):
+    """-> tests/golden/pmc_golden_cfg2.npz: K1 meta at policy_step 0.04, 16 seeded resets, 64 prop vectors, 64 rewards under PLE's default weights,
+    4 scripted episodes through env.step (history stacking at prop_dim 27).  Same key names as the first file, so the same checks read both."""
+    import contextlib
+    import io
+    out = OrderedDict()
+    rng = np.random.default_rng(20240808)
+    policy_step = 1.0 / CFG2_DEFAULTS['control_freq']
+    n_sub = int(policy_step / (1.0 / CFG2_DEFAULTS['sim_freq']))
+    out['cfg_prop_type'] = np.array(CFG2['prop_type'])
+    for k, v in CFG2_DEFAULTS.items():
+        out['cfg_' + k] = np.float64(v)
+    ml = MotionLib(MOCAP_DIR, policy_step)
+    out['k1_frame_step'] = np.float64(ml.frame_step)
+    out['k1_margin'] = np.int64(ml.margin)
+    out['k1_data_len'] = np.array(ml.data_len)
+    out['k1_max_steps'] = np.array(ml.max_steps)
+
+    env = create_tracking_game(**CFG2)
+    ple = env.env
+    client = ple._bullet_client
+    client.n_sub = n_sub
+    out['obs_space_shapes'] = np.array([ple.observation_space.spaces[k].shape[0] for k in ['prop', 'prop_a', 'future']])
+    obs_dim = int(out['obs_space_shapes'].sum())
+
+    g2 = dict(seed=[], clip=[], t0=[], obs=[], kin=[])
+    for seed in range(100, 116):
+        np.random.seed(seed)
+        ple._prioritized_sample_probability[:] = 1.0 / len(names)
+        o = env.reset()[0]
+        g2['seed'].append(seed); g2['clip'].append(ple.sampled_data_idx); g2['t0'].append(ple.time)
+        g2['obs'].append(obs_vec(o)); g2['kin'].append(state_vec(ple._legged_robot_kin.get_states_info()))
+    out.update({'g2_' + k: np.array(v) for k, v in g2.items()})
+
+    g3_state, g3_prop = [], []
+    for k in range(64):
+        s = rand_state(rng, big=(k % 4 == 0))
+        d = dict(base_pos=s[0:3], base_orn=s[3:7], base_lin_vel=s[7:10], base_ang_vel=s[10:13], joint_pos=list(s[13:25]), joint_vel=list(s[25:37]))
+        g3_state.append(s); g3_prop.append(ple._cfg_prop(ple._prepare_full_prop(d), CFG2['prop_type']))
+    out.update(g3_state=np.array(g3_state), g3_prop=np.array(g3_prop))
+
+    g4 = dict(dyn=[], kin=[], feet_dyn=[], feet_kin=[], reward=[])
+    for k in range(64):
+        kin = rand_state(rng)
+        scale = [0.02, 0.1, 0.3, 1.0][k % 4]
+        dyn = kin + rng.normal(size=37) * scale
+        dyn[3:7] = kin[3:7]
+        if k % 2:
+            from scipy.spatial.transform import Rotation as R
+            dyn[3:7] = (R.from_rotvec(rng.normal(size=3) * scale) * R.from_quat(kin[3:7])).as_quat()
+        fd = rng.uniform(-1, 1, (4, 3)); fk = fd + rng.normal(size=(4, 3)) * 0.05 * scale
+        set_dyn(client, dyn, 0); set_dyn(client, kin, 1)
+        client.feet[0], client.feet[1] = fd, fk
+        with contextlib.redirect_stdout(io.StringIO()):
+            r = ple._compute_reward()
+        for kk, v in zip(g4.keys(), [dyn, kin, fd, fk, r]):
+            g4[kk].append(v)
+    out.update({'g4_' + k: np.array(v) for k, v in g4.items()})
+
+    ep = dict(seed=[], clip=[], actions=[], dyn=[], feet_dyn=[], feet_kin=[], obs=[], reward=[], done=[], n=[],
+              prob_after=[], avg_len_after=[], reset_obs=[])
+    T, n_ep = 8, 4
+    ple._prioritized_sample_probability[:] = 1.0 / len(names)
+    ple._avg_reward_sum[:] = 0.0
+    for e in range(n_ep):
+        seed = 2000 + e
+        np.random.seed(seed)
+        with contextlib.redirect_stdout(io.StringIO()):
+            o0 = obs_vec(env.reset()[0])
+        kin0 = state_vec(ple._legged_robot_kin.get_states_info())
+        acts = rng.normal(size=(T, 12)) * 0.1353
+        dyn_seq, obs_seq, rew_seq, done_seq, fd_seq, fk_seq = [], [], [], [], [], []
+        n_done = T
+        for t in range(T):
+            s = kin0 + rng.normal(size=37) * 0.02 * (t + 1)          # drifts away from the reference; episodes 0 and 2 fall over at step 5
+            s[3:7] = kin0[3:7] / np.linalg.norm(kin0[3:7])
+            if e % 2 == 0 and t >= 5:
+                from scipy.spatial.transform import Rotation as R
+                s[3:7] = (R.from_quat(kin0[3:7]) * R.from_euler('x', 1.2)).as_quat()
+            fd = rng.uniform(-1, 1, (4, 3)); fk = fd + rng.normal(size=(4, 3)) * 0.01
+            client.script = [s]; client.feet[0], client.feet[1] = fd, fk
+            with contextlib.redirect_stdout(io.StringIO()):
+                (o,), (r,), d, info = env.step([acts[t]])
+            dyn_seq.append(s); obs_seq.append(obs_vec(o)); rew_seq.append(r); done_seq.append(d); fd_seq.append(fd); fk_seq.append(fk)
+            if d:
+                n_done = t + 1
+                break
+        pad = lambda a, shape: np.concatenate([np.array(a), np.zeros((T - len(a),) + shape)], 0)
+        ep['seed'].append(seed); ep['clip'].append(ple.sampled_data_idx)
+        ep['actions'].append(acts); ep['dyn'].append(pad(dyn_seq, (37,))); ep['obs'].append(pad(obs_seq, (obs_dim,)))
+        ep['feet_dyn'].append(pad(fd_seq, (4, 3))); ep['feet_kin'].append(pad(fk_seq, (4, 3)))
+        ep['reward'].append(pad(rew_seq, ())); ep['done'].append(pad(done_seq, ())); ep['n'].append(n_done)
+        ep['prob_after'].append(ple._prioritized_sample_probability.copy()); ep['avg_len_after'].append(ple.avg_episode_len.copy())
+        ep['reset_obs'].append(o0)
+    out.update({'g5_' + k: np.array(v) for k, v in ep.items()})
+    t0s = []                      # exact t0 of each scripted episode (time accumulates, so recompute from a fresh seeded reset)
+    for e in range(n_ep):
+        np.random.seed(2000 + e)
+        ple._prioritized_sample_probability[:] = 1.0 / len(names) if e == 0 else ep['prob_after'][e - 1]
+        env.reset(); t0s.append(ple.time)
+    out['g5_t0'] = np.array(t0s)
+    np.savez_compressed(os.path.join(HERE, 'pmc_golden_cfg2.npz'), **out)
+    print('wrote', os.path.join(HERE, 'pmc_golden_cfg2.npz'), {k: getattr(v, 'shape', None) for k, v in out.items()})
 
 
 def main():
@@ -358,6 +472,7 @@ def main():
 
     np.savez_compressed(os.path.join(HERE, 'pmc_golden.npz'), **out)
     print('wrote', os.path.join(HERE, 'pmc_golden.npz'), {k: getattr(v, 'shape', None) for k, v in out.items()})
+    second_config(create_tracking_game, MotionLib, LeggedRobot, names)
     print('K3 reward', out['k3_reward'], 'K4 t0', out['k4_t0'], 'sum|prop|', np.abs(out['k4_obs'][:99]).sum(), 'sum|future|', np.abs(out['k4_obs'][135:]).sum())
 
 

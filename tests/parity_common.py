@@ -30,6 +30,26 @@ def make_engine(model_blob, table, n_envs, lib_path=None, **kw):
     return capi.Engine(cfg, model_blob, table, lib_path=lib_path)
 
 
+def config_scalars(cfg=None):
+    """what the comparators restate of an env_config dict `cfg` (the keys of capi.make_config; None: the training scripts' point, the defaults of
+    make_engine / make_oracle_batch): kp, kd, max_tau, the substeps of one control step (PLE:52) and the prop_type list"""
+    c = dict(cfg or {})
+    n_sub = int((1.0 / float(c.get('control_freq', 50.0))) / (1.0 / float(c.get('sim_freq', 500.0))))
+    return dict(kp=float(c.get('kp', 50.0)), kd=float(c.get('kd', 0.5)), max_tau=float(c.get('max_tau', 18.0)), n_sub=n_sub,
+                prop_type=list(c.get('prop_type', PMC_PROP_TYPE)))
+
+
+def prop_layout(prop_type):
+    """observation columns by kind for a prop_type list (PLE:101-121: prop = 3 stacked frames of the keys in list order | prop_a 36 | future 72):
+    -> (prop_dim, configuration-like columns of the newest frame and every column of prop_a and future, velocity columns of the newest frame)"""
+    pd = sum(capi.PROP_SIZES[k] for k in prop_type)
+    conf, vel, off = [], [], 2 * pd
+    for k in prop_type:
+        (conf if k in ('joint_pos', 'e_g') else vel).extend(range(off, off + capi.PROP_SIZES[k]))
+        off += capi.PROP_SIZES[k]
+    return pd, np.array(conf + list(range(3 * pd, 3 * pd + 108)), dtype=int), np.array(vel, dtype=int)
+
+
 def quat_align(a, ref):
     """flip the sign of quaternion rows of `a` to match `ref` (q and -q are the same rotation)."""
     a = a.copy()
@@ -39,10 +59,11 @@ def quat_align(a, ref):
     return a
 
 
-def check_reset_against_goldens(golden, model_blob, table, lib_path):
-    """PLE:150-171 / ML:48-57 at explicit (clip, t0): first obs + ghost state vs the imported reference."""
+def check_reset_against_goldens(golden, model_blob, table, lib_path, cfg=None):
+    """PLE:150-171 / ML:48-57 at explicit (clip, t0): first obs + ghost state vs the imported reference.
+    cfg: the env_config the golden file was generated under (None: the training scripts' point); `table` is loaded at its 1 / control_freq."""
     n = len(golden['g2_seed'])
-    E = make_engine(model_blob, table, n, lib_path)
+    E = make_engine(model_blob, table, n, lib_path, **(cfg or {}))
     E.reset(clip=golden['g2_clip'], t0=golden['g2_t0'])
     np.testing.assert_allclose(E.obs(), golden['g2_obs'], rtol=NONPHYS_TOL, atol=NONPHYS_TOL)
     kin = quat_align(E.ref_state().astype(np.float64), golden['g2_kin'])
@@ -63,15 +84,15 @@ def check_reset_against_goldens(golden, model_blob, table, lib_path):
     E.close()
 
 
-def oracle_self_deviation(B1, pre, act, kp=50.0, kd=0.5, max_tau=18.0):
-    """How far the ORACLE's own result of one control step (ten substeps from state `pre` under the PD target of `act`) moves when its state is
+def oracle_self_deviation(B1, pre, act, kp=50.0, kd=0.5, max_tau=18.0, n_sub=10):
+    """How far the ORACLE's own result of one control step (n_sub substeps -- ten at 50 Hz -- from state `pre` under the PD target of `act`) moves when its state is
     perturbed at float32 resolution: rounded to float32 between substeps, and started from joint angles one float32 ulp up / down.  A step in
     which a contact makes or breaks, or sticks or slips, on the strength of the last bit amplifies such perturbations by orders of magnitude;
     no float32 implementation can then be closer to the float64 oracle than the oracle is to itself.  Returns (configuration, relative velocity)."""
     def ten(s0, r32=False):
         s = np.array(s0, dtype=np.float64)
         tgt = np.clip(s[13:25] + np.asarray(act, np.float64), -3.0, 3.0)
-        for _ in range(10):
+        for _ in range(n_sub):
             tau = np.clip(kp * (tgt - s[13:25]) - kd * s[25:37], -max_tau, max_tau)
             s = B1.substep(s, tau)[0]
             if r32:
@@ -89,13 +110,15 @@ def oracle_self_deviation(B1, pre, act, kp=50.0, kd=0.5, max_tau=18.0):
     return cc, cv, base
 
 
-def run_lockstep(golden, orc, model_blob, table, lib_path, n_envs, n_steps, seed, resync=True, sigma=SIGMA, policy=None, total_envs=None, spec=None):
+def run_lockstep(golden, orc, model_blob, table, lib_path, n_envs, n_steps, seed, resync=True, sigma=SIGMA, policy=None, total_envs=None, spec=None, cfg=None):
     """Step engine and oracle side by side from golden (clip, t0) starts with the same random actions.
     With resync the oracle is re-seeded with the engine's float32 state after every control step, so every step
     is an independent single-control-step comparison.
     total_envs: the engine runs that many envs (the larger-batch kernel builds start above 4096) and the oracle follows n_envs of
-    them, spread over the first, middle and last wavefronts of the grid."""
+    them, spread over the first, middle and last wavefronts of the grid.
+    cfg: env_config fields (the keys of capi.make_config) applied to BOTH the engine and the oracle; `table` is then loaded at 1 / control_freq."""
     rng = np.random.default_rng(seed)
+    kw = dict(cfg or {})
     N = total_envs or n_envs
     if total_envs:
         third = n_envs // 3
@@ -104,8 +127,8 @@ def run_lockstep(golden, orc, model_blob, table, lib_path, n_envs, n_steps, seed
         idx = np.arange(n_envs)
     pick = rng.integers(0, len(golden['g2_clip']), N)
     clip, t0 = golden['g2_clip'][pick], golden['g2_t0'][pick]
-    E = make_engine(model_blob, table, N, lib_path)
-    B = make_oracle_batch(orc, model_blob, table, n_envs=n_envs)
+    E = make_engine(model_blob, table, N, lib_path, **kw)
+    B = make_oracle_batch(orc, model_blob, table, n_envs=n_envs, **kw)
     if spec:                                 # a spec switch that exists in both implementations (include/llenv_model.h LLM_SPEC_*)
         E.set_spec(**spec)
         orc.reset_spec(); orc.set_spec(**spec)
@@ -114,9 +137,10 @@ def run_lockstep(golden, orc, model_blob, table, lib_path, n_envs, n_steps, seed
     for i in range(n_envs):
         B.reset_env(i, int(clip[idx[i]]), float(t0[idx[i]]))
         B.set_state(i, es0[idx[i]].astype(np.float64))
-    B2 = make_oracle_batch(orc, model_blob, table, n_envs=1)            # scratch env for the selection-tie re-runs below
+    B2 = make_oracle_batch(orc, model_blob, table, n_envs=1, **kw)      # scratch env for the selection-tie re-runs below
     stats = dict(config=[], vel=[], obs=[], obs_vel=[], reward=[], feet=[], done_mismatch=0, done=0, on_tie=0, ill=[])
-    kd_, max_tau_ = 0.5, 18.0                                           # make_engine / make_oracle_batch defaults (PMC config of SURVEY 8)
+    pd_ = config_scalars(cfg)                                           # (None: make_engine / make_oracle_batch defaults, the PMC config of SURVEY 8)
+    pdim, obs_conf, obs_vel = prop_layout(pd_.pop('prop_type'))
     prev_obs = None
     alive = np.ones(n_envs, bool)
     for t in range(n_steps):
@@ -157,7 +181,7 @@ def run_lockstep(golden, orc, model_blob, table, lib_path, n_envs, n_steps, seed
             ce, ve = max(err[0:7].max(), err[13:25].max()), max(err[7:13].max(), err[25:37].max()) / vscale
             if resync and (ce > PHYS_STEP_TOL or ve > 10 * PHYS_STEP_TOL):
                 # outside the bars: is the step ill-conditioned in the oracle itself?  (counted, printed, capped by the callers)
-                cc, cv, base = oracle_self_deviation(B2, pre, act[e], kd=kd_, max_tau=max_tau_)
+                cc, cv, base = oracle_self_deviation(B2, pre, act[e], **pd_)
                 assert np.abs(quat_align(base, os_) - os_).max() < 1e-9 or adopted, 'oracle_self_deviation does not restate step_env'
                 stats['ill'].append((ce, ve, cc, cv))
             stats['config'].append(max(err[0:7].max(), err[13:25].max()))
@@ -165,11 +189,12 @@ def run_lockstep(golden, orc, model_blob, table, lib_path, n_envs, n_steps, seed
             if adopted:                      # the engine's row choice was the other legitimate one: its observation follows its own state
                 oo = eo[e].astype(np.float64)
             oe = np.abs(eo[e] - oo)
-            # newest prop frame: joint_pos | joint_vel | ang_vel_loc | lin_vel_loc | e_g  (PMC_PROP_TYPE order)
-            stats['obs'].append(max(oe[66:78].max(), oe[96:99].max(), oe[99:].max()))            # configuration-like entries
-            stats['obs_vel'].append(oe[78:96].max() / vscale)                                      # velocity entries
+            # newest prop frame, the keys in prop_type order (PMC_PROP_TYPE: joint_pos 66:78 | joint_vel 78:90 | ang_vel_loc | lin_vel_loc 90:96 | e_g 96:99)
+            stats['obs'].append(oe[obs_conf].max())                                                # configuration-like entries, prop_a and future
+            stats['obs_vel'].append(oe[obs_vel].max() / vscale if len(obs_vel) else 0.0)           # velocity entries
             if prev_obs is not None:                                                               # deque shift, bit exact
-                assert np.array_equal(eo[e][0:66], prev_obs[e][33:99]) and np.array_equal(eo[e][99:123], prev_obs[e][111:135])
+                assert np.array_equal(eo[e][0:2 * pdim], prev_obs[e][pdim:3 * pdim])
+                assert np.array_equal(eo[e][3 * pdim:3 * pdim + 24], prev_obs[e][3 * pdim + 12:3 * pdim + 36])
             if not adopted:
                 stats['reward'].append(abs(er[e] - orr))
                 ofd, ofk = B.get_feet(i)
@@ -207,8 +232,8 @@ def bars_with_conditioning(st, label, vel_hi=10 * PHYS_STEP_TOL):
         assert ce <= max(PHYS_STEP_TOL, ILL_FACTOR * cc) and ve <= max(vel_hi, ILL_FACTOR * cv), (label, 'engine error', ce, ve, 'oracle self-deviation', cc, cv)
 
 
-def check_single_step_parity(golden, orc, model_blob, table, lib_path, n_envs=32, n_steps=12, seed=7, total_envs=None, spec=None):
-    st = run_lockstep(golden, orc, model_blob, table, lib_path, n_envs, n_steps, seed, resync=True, total_envs=total_envs, spec=spec)
+def check_single_step_parity(golden, orc, model_blob, table, lib_path, n_envs=32, n_steps=12, seed=7, total_envs=None, spec=None, cfg=None):
+    st = run_lockstep(golden, orc, model_blob, table, lib_path, n_envs, n_steps, seed, resync=True, total_envs=total_envs, spec=spec, cfg=cfg)
     assert len(st['config']) > n_envs * n_steps * 0.5
     assert st['on_tie'] <= max(2, len(st['config']) // 500), st['on_tie']          # samples on the selection rule's discontinuity: counted, capped (observed: 0 - 1 per run)
     # EVERY sample: configuration within 1e-4, velocities within 1e-3 of (1 + the env's largest joint rate); and at most 1 % of the env-steps
@@ -378,7 +403,7 @@ def check_trained_policy_tracks(lib_path, n_envs=16, n_steps=200, seed=7):
     return dict(mean_reward=mean_r, tracked=ok.mean(), steps=steps, why=why)
 
 
-def check_trajectory_ring(model_blob, table, lib_path, read_ring, write_dev=None):
+def check_trajectory_ring(model_blob, table, lib_path, read_ring, write_dev=None, cfg=None):
     """ll_enable_unrolls: every step writes its transition into time step (s mod unroll) of block ((s div unroll) mod 2) of the
     env's unroll -- X in the learner's flatten order (future | prop | prop_a), A, neglogp, R, V, r, 1 - done -- and ll_finish_unroll
     fills R with the TD(lambda) returns.  read_ring(address, shape) -> numpy copy (host memory for the emulation library, device
@@ -387,7 +412,7 @@ def check_trajectory_ring(model_blob, table, lib_path, read_ring, write_dev=None
     from conftest import GOLDEN_DIR
     from lifelike_agility_and_play_amd import gather
     n, unroll = 24, 4
-    E = make_engine(model_blob, table, n, lib_path, auto_reset=1, seed=5)
+    E = make_engine(model_blob, table, n, lib_path, auto_reset=1, seed=5, **(cfg or {}))
     E.reset()
     ptr, w = E.enable_unrolls(unroll, 2)
     od = E.obs_dim
@@ -468,7 +493,7 @@ def check_trajectory_ring(model_blob, table, lib_path, read_ring, write_dev=None
     assert list(g['shapes']) == [72, 99, 36, 12]
 
 
-def check_multi_step_launch(model_blob, table, lib_path, read_ring, sizes=(24,), k=7, n_launches=5, spec=None, obstacle=False):
+def check_multi_step_launch(model_blob, table, lib_path, read_ring, sizes=(24,), k=7, n_launches=5, spec=None, obstacle=False, cfg=None):
     """ll_step_random_n(sigma, k) == k x ll_step_random(sigma), bit for bit -- state, ghost, observation, reward, done reasons, bookkeeping,
     counters, episode histogram, the recorded actions, every row of the unroll buffers and the sampling table -- with uniform sampling and
     auto-reset, with prioritized sampling without auto-reset, and (round 5) WITH BOTH: the table is folded after every control step of a launch
@@ -477,6 +502,7 @@ def check_multi_step_launch(model_blob, table, lib_path, read_ring, sizes=(24,),
     obstacle: the same with set_obstacle (the jump obstacle's builds)."""
     unroll = 4
     okw = dict(set_obstacle=True, obstacle_height=0.2) if obstacle else {}
+    okw.update(cfg or {})                                            # env_config fields of every engine of the check
     for n in sizes:
         for kw in (dict(auto_reset=1, prioritized_sample_factor=0.0), dict(auto_reset=0, prioritized_sample_factor=3.0),
                    dict(auto_reset=1, prioritized_sample_factor=3.0), dict(auto_reset=1, prioritized_sample_factor=3.0 + 1e-9)):
@@ -533,7 +559,7 @@ def check_multi_step_launch(model_blob, table, lib_path, read_ring, sizes=(24,),
         C.close()
 
 
-def check_obstacle_variant(golden, orc, model_blob, table, lib_path, n_envs=24, n_steps=60, seed=2, total_envs=None, spec=None, cap_ill=0, pct=100):
+def check_obstacle_variant(golden, orc, model_blob, table, lib_path, n_envs=24, n_steps=60, seed=2, total_envs=None, spec=None, cap_ill=0, pct=100, cfg=None):
     """set_obstacle=True (PLE:173-193, :262-268, :341-346): engine vs oracle on the jump clips, random policy.  The robot does
     not clear the box, so episodes must end with the COLLISION bit in both, at the same step.
     total_envs: the engine runs that many envs (above 4096: the larger-batch build of the obstacle kernel) and the oracle follows n_envs of them,
@@ -550,7 +576,7 @@ def check_obstacle_variant(golden, orc, model_blob, table, lib_path, n_envs=24, 
     # start shortly before a jump peak: the robot inherits the mocap velocity and flies into the box
     t0 = np.array([max(0.0, tab[off[c] + rng.integers(0, cnt[c]), 3] - 0.2) for c in clip])
     t0 = np.minimum(t0, [table.frame_step * (table.clip_len[c] - table.margin - 2) for c in clip])
-    kw = dict(set_obstacle=True, obstacle_height=0.2)
+    kw = dict(set_obstacle=True, obstacle_height=0.2, **(cfg or {}))         # cfg: env_config fields on BOTH sides; `table` loaded at 1 / control_freq
     N = total_envs or n_envs
     third = n_envs // 3
     idx = np.arange(n_envs) if not total_envs else np.concatenate([np.arange(third), N // 2 - 7 + np.arange(third), N - (n_envs - 2 * third) + np.arange(n_envs - 2 * third)])
@@ -563,15 +589,16 @@ def check_obstacle_variant(golden, orc, model_blob, table, lib_path, n_envs=24, 
         E.set_spec(**spec)
         orc.reset_spec(); orc.set_spec(**spec)
     try:
-        return _run_obstacle_variant(E, B, rng, clip, t0, clip_all, t0_all, idx, n_envs, n_steps, orc, model_blob, table, cap_ill, pct)
+        return _run_obstacle_variant(E, B, rng, clip, t0, clip_all, t0_all, idx, n_envs, n_steps, orc, model_blob, table, cap_ill, pct, cfg)
     finally:
         if spec:
             orc.reset_spec()
 
 
-def _run_obstacle_variant(E, B, rng, clip, t0, clip_all, t0_all, idx, n_envs, n_steps, orc, model_blob, table, cap_ill, pct):
+def _run_obstacle_variant(E, B, rng, clip, t0, clip_all, t0_all, idx, n_envs, n_steps, orc, model_blob, table, cap_ill, pct, cfg=None):
     N = E.n_envs
-    B2 = make_oracle_batch(orc, model_blob, table, n_envs=1)            # the oracle's own deviation (oracle_self_deviation) of a sample outside the bars
+    pd_ = config_scalars(cfg); pd_.pop('prop_type')
+    B2 = make_oracle_batch(orc, model_blob, table, n_envs=1, **(cfg or {}))   # the oracle's own deviation (oracle_self_deviation) of a sample outside the bars
     ill = []
     E.reset(clip=clip_all, t0=t0_all)
     es0 = E.state()
@@ -600,7 +627,7 @@ def _run_obstacle_variant(E, B, rng, clip, t0, clip_all, t0_all, idx, n_envs, n_
             if cap_ill and (ce >= 1e-4 or ve >= 1e-3):
                 # outside the bars: is the step ill-conditioned in the oracle itself?  Only a step the box took no part in is restated by
                 # oracle_self_deviation (the plain batch): one it did take part in stays held to the bars.
-                cc, cv, base = oracle_self_deviation(B2, pre, act[i])
+                cc, cv, base = oracle_self_deviation(B2, pre, act[i], **pd_)
                 if np.abs(quat_align(base, os_) - os_).max() < 1e-9:
                     ill.append((ce, ve, cc, cv))
                     assert ce <= max(1e-4, ILL_FACTOR * cc) and ve <= max(1e-3, ILL_FACTOR * cv), ('engine error', ce, ve, 'oracle self-deviation', cc, cv)
@@ -707,13 +734,13 @@ def check_deep_penetration_against_oracle(orc, model_blob, table, lib_path, spec
         E.close()
 
 
-def check_scripted_episodes_against_goldens(golden, model_blob, table, lib_path):
+def check_scripted_episodes_against_goldens(golden, model_blob, table, lib_path, cfg=None, min_done=6):
     """The engine's whole step() control flow against the REFERENCE's own outputs (golden G5): 12 scripted episodes driven
     exactly as gen_golden.py drove the reference through its fake BulletClient -- physics result and foot positions
     supplied, everything else (time keeping with the Q2 phase lag, mocap lookup, history stacking with raw actions,
     5-term reward, the termination tests, PLE:235-240 table update) computed by the kernel."""
     n_ep = len(golden['g5_seed'])
-    E = make_engine(model_blob, table, 1, lib_path)
+    E = make_engine(model_blob, table, 1, lib_path, **(cfg or {}))
     n_done = 0
     for e in range(n_ep):
         E.reset(clip=[int(golden['g5_clip'][e])], t0=[float(golden['g5_t0'][e])])
@@ -733,10 +760,10 @@ def check_scripted_episodes_against_goldens(golden, model_blob, table, lib_path)
         np.testing.assert_allclose(prob, golden['g5_prob_after'][e], rtol=1e-5, atol=1e-8)       # PLE:239-240
         np.testing.assert_allclose(avg_len, golden['g5_avg_len_after'][e], rtol=1e-6, atol=1e-9)  # PLE:237
     E.close()
-    assert n_done >= 6
+    assert n_done >= min_done
 
 
-def check_auto_reset_equals_manual_reset(model_blob, table, lib_path, n_envs=24, n_steps=40):
+def check_auto_reset_equals_manual_reset(model_blob, table, lib_path, n_envs=24, n_steps=40, cfg=None):
     """An env that finishes under auto_reset=1 is re-seeded INSIDE the step kernel (the merged tail of step_env); the same
     episode driven with auto_reset=0 and an explicit ll_reset at the engine-chosen (clip, t0) must give the same
     observation, state, ghost, feet and bookkeeping.  With keep_terminal_obs the finished episode's last observation must be
@@ -748,8 +775,8 @@ def check_auto_reset_equals_manual_reset(model_blob, table, lib_path, n_envs=24,
             np.testing.assert_array_equal(x, y)
         else:
             np.testing.assert_allclose(x, y, rtol=2e-6, atol=2e-6)
-    A = make_engine(model_blob, table, n_envs, lib_path, auto_reset=1, seed=21, keep_terminal_obs=True)
-    B = make_engine(model_blob, table, n_envs, lib_path, auto_reset=0, seed=21)
+    A = make_engine(model_blob, table, n_envs, lib_path, auto_reset=1, seed=21, keep_terminal_obs=True, **(cfg or {}))
+    B = make_engine(model_blob, table, n_envs, lib_path, auto_reset=0, seed=21, **(cfg or {}))
     A.reset(); B.reset()
     assert np.array_equal(A.obs(), B.obs())
     rng = np.random.default_rng(5)
@@ -777,7 +804,7 @@ def check_auto_reset_equals_manual_reset(model_blob, table, lib_path, n_envs=24,
         ia, ib = A.episode_info(), B.episode_info()
         for k in ('clip', 'time', 'steps', 'reward_sum'):
             same(ia[k], ib[k])
-    C = make_engine(model_blob, table, 4, lib_path, auto_reset=1)
+    C = make_engine(model_blob, table, 4, lib_path, auto_reset=1, **(cfg or {}))
     C.reset()
     try:
         C.terminal_obs()
@@ -863,7 +890,7 @@ def check_engine_against_host_build(model_blob, table, emul_lib, n_envs=4096, st
     return out
 
 
-def check_self_collision_parity(golden, orc, model_blob, table, lib_path, n_envs=16, seed=5, spec=None):
+def check_self_collision_parity(golden, orc, model_blob, table, lib_path, n_envs=16, seed=5, spec=None, cfg=None):
     """Legs driven into one another in mid-air (same-side front/hind pairs, left/right pairs, diagonal): one control step,
     engine vs oracle -- same capsule spec, different formulations -- and the oracle WITHOUT self-collision as the control: the
     legs must have been stopped, not passed through each other (LR:212-217 URDF_USE_SELF_COLLISION).
@@ -873,11 +900,12 @@ def check_self_collision_parity(golden, orc, model_blob, table, lib_path, n_envs
     from oracle import oracle as orc_mod
     rng = np.random.default_rng(seed)
     clip, t0 = golden['g2_clip'][:n_envs], golden['g2_t0'][:n_envs]
-    E = make_engine(model_blob, table, n_envs, lib_path)
+    kw = dict(cfg or {})                                      # env_config fields on BOTH sides
+    E = make_engine(model_blob, table, n_envs, lib_path, **kw)
     if spec:
         E.set_spec(**spec)
-    B = make_oracle_batch(orc, model_blob, table, n_envs=n_envs)
-    B0 = make_oracle_batch(orc, model_blob, table, n_envs=n_envs)
+    B = make_oracle_batch(orc, model_blob, table, n_envs=n_envs, **kw)
+    B0 = make_oracle_batch(orc, model_blob, table, n_envs=n_envs, **kw)
     E.reset(clip=clip, t0=t0)
     st = E.state().astype(np.float64)
     act = np.zeros((n_envs, 12), np.float32)
@@ -916,7 +944,7 @@ def check_self_collision_parity(golden, orc, model_blob, table, lib_path, n_envs
     orc.reset_spec()
     for i in range(n_envs):
         if spec:
-            plain = make_oracle_batch(orc, model_blob, table, n_envs=1)                 # the spec's own answer (without the switches), for `moved`
+            plain = make_oracle_batch(orc, model_blob, table, n_envs=1, **kw)           # the spec's own answer (without the switches), for `moved`
             plain.reset_env(0, int(clip[i]), float(t0[i])); plain.set_state(0, st32[i])
             plain.step_env(0, act[i].astype(np.float64))
             orc.set_spec(**spec)

@@ -167,6 +167,10 @@ def draws_to_uniforms(log):
 
 def make_engine(cfg_dict, n_arenas, lib_path, **kw):
     from lifelike_agility_and_play_amd import sepmc_capi, urdf_model
+    from epmc_parity_common import with_base_cfg
+    cfg_dict = with_base_cfg(cfg_dict)                      # (epmc_parity_common.cfg_variant)
+    if 'solver_iterations' in cfg_dict:
+        kw.setdefault('solver_iterations', cfg_dict.pop('solver_iterations'))
     cfg = sepmc_capi.make_sepmc_config(n_arenas, cfg_dict, **kw)
     E = sepmc_capi.SepmcEngine(cfg, urdf_model.default_model_blob(), lib_path=lib_path)
     from epmc_parity_common import BASE_SPEC
@@ -714,6 +718,8 @@ def _check_pair_physics_against_oracle(lib_path, n_arenas, seed, total_arenas, c
     from oracle import oracle as orc
     from lifelike_agility_and_play_amd import mocap, urdf_model
     from parity_common import quat_align
+    from epmc_parity_common import oracle_kw, pd_scalars
+    kp, kd, max_tau, n_sub = pd_scalars()                   # (epmc_parity_common.cfg_variant; 50, 0.5, 16 and ten substeps without one)
     cfg = env_config((1, 0, 0))
     cfg['env_randomize_config']['disturb_force_config'] = {'start_time': 0.0, 'interval_time': 1.0, 'duration_time': 0.5, 'horizontal_force': [10, 50], 'vertical_force': [0, 10]}
     NA = total_arenas or n_arenas
@@ -746,7 +752,7 @@ def _check_pair_physics_against_oracle(lib_path, n_arenas, seed, total_arenas, c
     E.step_host(act)
     es = E.state().astype(np.float64)
     tr = E.push_trace().astype(np.float64)
-    B = make_oracle_batch(orc, urdf_model.default_model_blob(), mocap.load_mocap('', 0.02), n_envs=1, kd=0.5, max_tau=16.0)
+    B = make_oracle_batch(orc, urdf_model.default_model_blob(), mocap.load_mocap('', 0.02), n_envs=1, **oracle_kw())
     out = dict(config=[], vel=[], n_rows=0, n_felt=0, who=[])
     ep_after = E.episode()
     for a in idx:
@@ -766,10 +772,10 @@ def _check_pair_physics_against_oracle(lib_path, n_arenas, seed, total_arenas, c
         tgt = [np.clip(s[r][13:25] + act[a, r].astype(np.float64), -3.0, 3.0) for r in range(2)]
         mu = float(np.float32(ep['friction'][a]) * np.float32(0.9))
         nrows = 0
-        for k in range(10):
-            tau = [np.clip(50.0 * (tgt[r] - s[r][13:25]) - 0.5 * s[r][25:37], -16.0, 16.0) for r in range(2)]
+        for k in range(n_sub):
+            tau = [np.clip(kp * (tgt[r] - s[r][13:25]) - kd * s[r][25:37], -max_tau, max_tau) for r in range(2)]
             push = [tr[a, r, k, 1:4] if tr[a, r, k, 0] > 0.5 else None for r in range(2)]
-            if k == 9:                          # the contact list the env reads is that of the last substep's collision detection (CTG:426-450)
+            if k == n_sub - 1:                          # the contact list the env reads is that of the last substep's collision detection (CTG:426-450)
                 tc = B.touch(s[0], s[1], near[0], flag_at[0], near[1], flag_at[1])
                 who = [1 if tc[r][0] else (2 if tc[r][1] else ((4 - r) if tc[r][2] else -1)) for r in range(2)]
                 taker = 1 if ep['with_flag0'][a] > 0.5 else 0
@@ -777,7 +783,7 @@ def _check_pair_physics_against_oracle(lib_path, n_arenas, seed, total_arenas, c
             s[0], s[1], pr = B.substep_pair(s[0], s[1], tau[0], tau[1], mu, near[0], near[1], 0.5 / 0.9, push[0], push[1])
             nrows += len(pr)
             for r in range(2):                                   # the same step with the other robot ignored
-                tf = np.clip(50.0 * (tgt[r] - s_free[r][13:25]) - 0.5 * s_free[r][25:37], -16.0, 16.0)
+                tf = np.clip(kp * (tgt[r] - s_free[r][13:25]) - kd * s_free[r][25:37], -max_tau, max_tau)
                 s_free[r], _, _ = B.substep_terrain(s_free[r], tf, mu, near[r], 0.5 / 0.9, push[r])
         out['n_rows'] += 1 if nrows else 0
         if max(np.abs(s[r] - s_free[r]).max() for r in range(2)) > 1e-3:
@@ -825,7 +831,7 @@ def arena_records(rows_a, cnt_a, ep, a):
 
 
 def oracle_pair_step(B, st_pair, act_pair, rec, mu, push_trace, r32=False, ulp=0):
-    """One control step (ten substeps) of the oracle's two-robot physics from the given states; r32 rounds both states to float32 between
+    """One control step (ten substeps at 50 Hz) of the oracle's two-robot physics from the given states; r32 rounds both states to float32 between
     substeps -- how far that moves the result is the step's conditioning in the oracle itself."""
     near, s = [], []
     for r in range(2):
@@ -837,8 +843,10 @@ def oracle_pair_step(B, st_pair, act_pair, rec, mu, push_trace, r32=False, ulp=0
         x = s[0].astype(np.float32)
         x[0:3] = np.nextafter(x[0:3], np.float32(np.inf * ulp)); x[13:25] = np.nextafter(x[13:25], np.float32(np.inf * ulp))
         s[0] = x.astype(np.float64)
-    for k in range(10):
-        tau = [np.clip(50.0 * (tgt[r] - s[r][13:25]) - 0.5 * s[r][25:37], -16.0, 16.0) for r in range(2)]
+    from epmc_parity_common import pd_scalars
+    kp, kd, max_tau, n_sub = pd_scalars()
+    for k in range(n_sub):
+        tau = [np.clip(kp * (tgt[r] - s[r][13:25]) - kd * s[r][25:37], -max_tau, max_tau) for r in range(2)]
         push = [push_trace[r, k, 1:4] if push_trace[r, k, 0] > 0.5 else None for r in range(2)]
         s[0], s[1], _ = B.substep_pair(s[0], s[1], tau[0], tau[1], mu, near[0], near[1], 0.5 / 0.9, push[0], push[1])
         if r32:
@@ -857,9 +865,10 @@ def check_free_running_against_oracle_env(lib_path, n_steps=4, prop_type=None, e
     worst = dict(state=0.0, percep_same=1.0, ill_conditioned=0)
     from conftest import make_oracle_batch
     from oracle import oracle as orc
-    B1 = make_oracle_batch(orc, blob, table, n_envs=1, kd=0.5, max_tau=16.0)
+    from epmc_parity_common import oracle_kw, with_base_cfg
+    B1 = make_oracle_batch(orc, blob, table, n_envs=1, **oracle_kw())
     for elements in element_sets:
-        cfg = env_config(elements, noisy)
+        cfg = with_base_cfg(env_config(elements, noisy))
         if prop_type is not None:
             cfg['prop_type'] = list(prop_type)
         P3 = 3 * sum({'joint_pos': 12, 'joint_vel': 12, 'root_lin_vel_loc': 3, 'root_ang_vel_loc': 3, 'e_g': 3}[k] for k in cfg['prop_type']) + 36   # prop | prop_a

@@ -148,3 +148,82 @@ def test_g7_obstacle_extraction(golden, mocap_table):
     yaw = R.from_quat(golden['g7_pose'][:, 3:7]).as_euler('xyz')[:, 2]
     assert np.abs(np.angle(np.exp(1j * (tab[:, 2] - yaw)))).max() < 1e-12
     np.testing.assert_array_equal(golden['g7_pose'][:, 2], 0.0)           # boxes sit on the ground (obstacle.py:28)
+
+
+# ---- the second pass of gen_golden.py: the factory's defaults (25 Hz, kd 1.0, PLE's reward weights) with a permuted subset prop_type ----------------
+
+def _cfg2():
+    import os
+    from conftest import GOLDEN_DIR
+    from lifelike_agility_and_play_amd import mocap
+    g = np.load(os.path.join(GOLDEN_DIR, 'pmc_golden_cfg2.npz'), allow_pickle=False)
+    cfg = dict(control_freq=float(g['cfg_control_freq']), sim_freq=float(g['cfg_sim_freq']), kp=float(g['cfg_kp']), kd=float(g['cfg_kd']),
+               max_tau=float(g['cfg_max_tau']), prioritized_sample_factor=float(g['cfg_prioritized_sample_factor']),
+               prop_type=[str(k) for k in g['cfg_prop_type']], reward_weights=None)
+    assert (cfg['control_freq'], cfg['kd'], cfg['prop_type']) == (25.0, 1.0, ['e_g', 'joint_vel', 'joint_pos'])
+    return g, cfg, mocap.load_mocap('', 1.0 / cfg['control_freq'])
+
+
+def test_cfg2_k1_motionlib_meta(orc, model_blob):
+    g, cfg, table = _cfg2()
+    B = make_oracle_batch(orc, model_blob, table, **cfg)
+    margin, frame_rate, max_steps = B.meta()
+    assert margin == int(g['k1_margin']) == table.margin == 127           # ML:35 at policy_step 0.04
+    assert frame_rate == 120 and table.frame_step == float(g['k1_frame_step'])
+    np.testing.assert_allclose(max_steps, g['k1_max_steps'], rtol=1e-15)
+    np.testing.assert_allclose(table.max_steps, g['k1_max_steps'], rtol=1e-15)
+    assert B.obs_dim == int(g['obs_space_shapes'].sum()) == 189 and list(g['obs_space_shapes']) == [81, 36, 72]
+
+
+def test_cfg2_g2_reset_obs(orc, model_blob):
+    g, cfg, table = _cfg2()
+    B = make_oracle_batch(orc, model_blob, table, **cfg)
+    assert len(g['g2_seed']) == 16
+    for k in range(16):
+        obs = B.reset_env(0, int(g['g2_clip'][k]), float(g['g2_t0'][k]))
+        np.testing.assert_allclose(obs, g['g2_obs'][k], **OBS)
+        kin, ref = B.get_ref_state(0), g['g2_kin'][k]
+        assert quat_close(kin[3:7], ref[3:7], 1e-12)
+        np.testing.assert_allclose(np.delete(kin, [3, 4, 5, 6]), np.delete(ref, [3, 4, 5, 6]), **OBS)
+
+
+def test_cfg2_g3_prop(orc):
+    g, cfg, _ = _cfg2()
+    order = tuple(orc.PROP_IDS[k] for k in cfg['prop_type'])
+    assert len(g['g3_state']) == 64
+    for k in range(64):
+        p = orc.prop(g['g3_state'][k], order)
+        assert p.shape == (27,)
+        np.testing.assert_allclose(p, g['g3_prop'][k], **TIGHT)
+
+
+def test_cfg2_g4_reward_under_the_default_weights(orc):
+    g, _, _ = _cfg2()
+    from lifelike_agility_and_play_amd import capi
+    w = [capi.PLE_DEFAULT_REWARD_WEIGHTS[k] for k in capi.RW_KEYS]
+    assert len(g['g4_dyn']) == 64
+    for k in range(64):
+        r = orc.reward(g['g4_dyn'][k], g['g4_kin'][k], g['g4_feet_dyn'][k], g['g4_feet_kin'][k], w)
+        assert abs(r - float(g['g4_reward'][k])) < 1e-12, k
+    # ... and the weights matter: the training scripts' set gives other numbers
+    assert max(abs(orc.reward(g['g4_dyn'][k], g['g4_kin'][k], g['g4_feet_dyn'][k], g['g4_feet_kin'][k], RW) - float(g['g4_reward'][k])) for k in range(64)) > 1e-3
+
+
+def test_cfg2_g5_scripted_episodes(orc, model_blob):
+    """step() at 20 substeps per control step with the history stacked at prop_dim 27, against the reference's own env.step"""
+    g, cfg, table = _cfg2()
+    B = make_oracle_batch(orc, model_blob, table, **cfg)
+    n_done = 0
+    for e in range(len(g['g5_seed'])):
+        obs0 = B.reset_env(0, int(g['g5_clip'][e]), float(g['g5_t0'][e]))
+        np.testing.assert_allclose(obs0, g['g5_reset_obs'][e], **OBS)
+        for t in range(int(g['g5_n'][e])):
+            obs, r, d = B.step_env(0, g['g5_actions'][e, t], scripted_dyn=g['g5_dyn'][e, t], feet_dyn=g['g5_feet_dyn'][e, t], feet_kin=g['g5_feet_kin'][e, t])
+            np.testing.assert_allclose(obs, g['g5_obs'][e, t], err_msg='ep %d step %d' % (e, t), **OBS)
+            assert abs(r - g['g5_reward'][e, t]) < 1e-11
+            assert d == bool(g['g5_done'][e, t]), (e, t)
+        n_done += d
+        prob, _, avg_len = B.sampling_table()
+        np.testing.assert_allclose(prob, g['g5_prob_after'][e], rtol=1e-10, atol=1e-14)
+        np.testing.assert_allclose(avg_len, g['g5_avg_len_after'][e], rtol=1e-12)
+    assert len(g['g5_seed']) == 4 and n_done >= 2
