@@ -100,6 +100,14 @@ int ll_hl_policy_act_pg(ll_hl_policy* p, const float* d_obs, int obs_stride, con
 /* host copies of the value state [max_rows][64] (c | h); LL_EINVAL without an attached branch; both wait for the device to be idle first */
 int ll_hl_policy_get_value_state(ll_hl_policy* p, float* h_state);
 int ll_hl_policy_set_value_state(ll_hl_policy* p, const float* h_state);
+/*
+ * A new model for a policy in use: replaces the weights (and, when a value branch is attached, the branch: h_vf_weights is then required;
+ * without a branch it must be NULL) and touches no recurrent state -- the actor's pull of fresh weights every update_model_freq steps
+ * (distill_actor.py:294-308).  Same float counts as create / attach_value.  The upload is ordered on hip_stream, from a pinned staging
+ * buffer the policy owns: the call neither waits for the device nor races a launch queued on that stream before it; a second call waits
+ * for the first upload only.
+ */
+int ll_hl_policy_set_weights(ll_hl_policy* p, const float* h_weights, int n_floats, const float* h_vf_weights, int n_vf_floats, void* hip_stream);
 /* HIP-event time of the ll_hl_policy_act and ll_hl_policy_act_pg launches since the last call (like ll_policy_time_ms) */
 int ll_hl_policy_enable_timing(ll_hl_policy* p, int on);
 int ll_hl_policy_time_ms(ll_hl_policy* p, double* avg_ms, int* n_launches);

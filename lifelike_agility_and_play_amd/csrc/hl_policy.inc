@@ -17,6 +17,17 @@ struct HlW {
   const float* zero;              // 256 zeros: the bias of the LSTM's two bias-free products
 };
 
+// Which rows the 16 columns of a workgroup are.  row(m): the row whose observation, reset flag, outputs and Philox counters column m carries;
+// srow(m): where that column's recurrent state and value live; live(m): the column holds a row at all.  HlDense is rows row0 .. row0 + 15 of
+// n_rows (ll_hl_policy_act / _act_pg); hl_league.inc has the list map.  The helpers below also take the weights as a type: anything with
+// a[k] and zero.
+struct HlDense {
+  int row0, n_rows;
+  __device__ __forceinline__ int row(int m) const { return row0 + m; }
+  __device__ __forceinline__ int srow(int m) const { return row0 + m; }
+  __device__ __forceinline__ bool live(int m) const { return row0 + m < n_rows; }
+};
+
 __host__ __device__ constexpr int hl_same_out(int n, int s) { return (n + s - 1) / s; }
 // tf SAME padding: pad_total = max((out - 1) s + k - n, 0), the smaller half in front (oracle/epmc_policy.py _same_pad)
 __host__ __device__ constexpr int hl_same_front(int n, int k, int s) {
@@ -55,15 +66,16 @@ __device__ __forceinline__ void hl_conv(In in, const float* __restrict__ w, cons
 
 // percep_2d_encoder (epmc_net.py): 25x13x1 -> relu 1x1 (4) -> relu 4x4/2 (13x7x4) -> relu 2x2/2 (7x4x4) -> relu 2x2/1 (7x4x1) = 28 values,
 // written to feat rows f0 .. f0 + 27.  Weights: arrays k .. k + 7.  scr: >= 7616 floats of LDS.
-__device__ __forceinline__ void hl_enc2d(const HlW& W, int k, const float* __restrict__ obs, int stride, int col, int row0, int n_rows, float* scr,
-                                         float* feat, int f0, int tid) {
+template <class WT, class RM>
+__device__ __forceinline__ void hl_enc2d(const WT& W, int k, const float* __restrict__ obs, int stride, int col, const RM& R, float* scr, float* feat, int f0,
+                                         int tid) {
   float* s1 = scr;                       // [16][13 * 7][4]
   float* s2 = scr + POL_M * 91 * 4;      // [16][7 * 4][4]
   const float *w1 = W.a[k], *b1 = W.a[k + 1];
   hl_conv<25, 13, 4, 4, 4, 4, 2>(
       [&](int m, int y, int x, float* v) {
-        const int r = row0 + m;
-        const float g = r < n_rows ? obs[(long)r * stride + col + y * 13 + x] : 0.0f;
+        const int r = R.row(m);
+        const float g = R.live(m) ? obs[(long)r * stride + col + y * 13 + x] : 0.0f;
 #pragma unroll
         for (int c = 0; c < 4; c++) v[c] = fmaxf(fmaf(g, w1[c], b1[c]), 0.0f);
       },
@@ -93,17 +105,19 @@ __device__ __forceinline__ void hl_enc2d(const HlW& W, int k, const float* __res
 // percep_1d_encoder: 128 lidar values, periodic padding by 4 on both sides, relu conv 4 (1 -> 4) cropped back to 128, relu 4/2 (64x4),
 // relu 4/2 (32x4), relu 4/1 (32x1) -> feat rows f0 .. f0 + 31.  Weights: arrays k .. k + 7.  The first layer is evaluated where the
 // second reads it: on the 136-column padded input its SAME front pad is 1, so cropped position q sees lidar columns q - 1 .. q + 2 mod 128.
-__device__ __forceinline__ void hl_enc1d(const HlW& W, int k, const float* __restrict__ obs, int stride, int col, int row0, int n_rows, float* scr,
-                                         float* feat, int f0, int tid) {
+template <class WT, class RM>
+__device__ __forceinline__ void hl_enc1d(const WT& W, int k, const float* __restrict__ obs, int stride, int col, const RM& R, float* scr, float* feat, int f0,
+                                         int tid) {
   float* s1 = scr;                       // [16][64][4]
   float* s2 = scr + POL_M * 91 * 4;      // [16][32][4]
   const float *wa = W.a[k], *ba = W.a[k + 1];
   hl_conv<1, 128, 4, 4, 1, 4, 2>(
       [&](int m, int y, int q, float* v) {
-        const int r = row0 + m;
+        const int r = R.row(m);
+        const bool live = R.live(m);
         float g[4];
 #pragma unroll
-        for (int t = 0; t < 4; t++) g[t] = r < n_rows ? obs[(long)r * stride + col + ((q + t + 127) & 127)] : 0.0f;
+        for (int t = 0; t < 4; t++) g[t] = live ? obs[(long)r * stride + col + ((q + t + 127) & 127)] : 0.0f;
 #pragma unroll
         for (int c = 0; c < 4; c++) {
           float a = ba[c];
@@ -137,13 +151,13 @@ __device__ __forceinline__ void hl_enc1d(const HlW& W, int k, const float* __res
 
 // the three percept stacks of one encoder (weights k: 2-D k .. k+7, 1-D k+8 .. k+15, front k+16 .. k+23) -> feat rows
 // f0 .. f0+27 | f0+28 .. f0+59 | f0+60 .. f0+87.  Ends with a barrier.
-__device__ __forceinline__ void hl_percepts(const HlW& W, int k, const float* __restrict__ obs, int stride, int row0, int n_rows, float* scr, float* feat,
-                                            int f0, int tid) {
-  hl_enc2d(W, k, obs, stride, 135, row0, n_rows, scr, feat, f0, tid);
+template <class WT, class RM>
+__device__ __forceinline__ void hl_percepts(const WT& W, int k, const float* __restrict__ obs, int stride, const RM& R, float* scr, float* feat, int f0, int tid) {
+  hl_enc2d(W, k, obs, stride, 135, R, scr, feat, f0, tid);
   __syncthreads();
-  hl_enc1d(W, k + 8, obs, stride, 460, row0, n_rows, scr, feat, f0 + 28, tid);
+  hl_enc1d(W, k + 8, obs, stride, 460, R, scr, feat, f0 + 28, tid);
   __syncthreads();
-  hl_enc2d(W, k + 16, obs, stride, 588, row0, n_rows, scr, feat, f0 + 60, tid);
+  hl_enc2d(W, k + 16, obs, stride, 588, R, scr, feat, f0 + 60, tid);
   __syncthreads();
 }
 
@@ -155,12 +169,13 @@ __device__ __forceinline__ float hl_sum32(float v) {     // sum over the 32 lane
 
 __device__ __forceinline__ float hl_sigmoid(float x) { return 1.0f / (1.0f + expf(-x)); }
 
-// The state of one LSTM (c at st[0..31], h at st[32..63] of a row's state) into LDS k-major: cs, hs [32][16]; rows >= n_rows and rows
+// The state of one LSTM (c at st[0..31], h at st[32..63] of a row's state) into LDS k-major: cs, hs [32][16]; columns without a row and rows
 // flagged in reset start from zero.
-__device__ __forceinline__ void hl_load_state(const float* __restrict__ state, int sdim, int off, const uint8_t* __restrict__ reset, int row0, int n_rows,
-                                              float* cs, float* hs, int tid) {
-  const int m = tid >> 5, j = tid & 31, r = row0 + m;
-  const bool live = r < n_rows && !(reset && reset[r]);
+template <class RM>
+__device__ __forceinline__ void hl_load_state(const float* __restrict__ state, int sdim, int off, const uint8_t* __restrict__ reset, const RM& R, float* cs,
+                                              float* hs, int tid) {
+  const int m = tid >> 5, j = tid & 31, r = R.srow(m);
+  const bool live = R.live(m) && !(reset && reset[R.row(m)]);
   cs[j * POL_M + m] = live ? state[(long)r * sdim + off + j] : 0.0f;
   hs[j * POL_M + m] = live ? state[(long)r * sdim + off + 32 + j] : 0.0f;
 }
@@ -168,12 +183,13 @@ __device__ __forceinline__ void hl_load_state(const float* __restrict__ state, i
 // tpolicies lstm_embed_block, one step (oracle/epmc_policy.py): x [256][16] k-major in `x`; weights k0 .. k0+8 = wx, wh, b, beta_x, gamma_x,
 // beta_h, gamma_h, beta_c, gamma_c.  zbuf: 256 x 16 floats of scratch.  Leaves c', h' in cs, hs and in the state buffer; returns h'_j of
 // this lane's (row, unit).  Starts and ends at a barrier.
-__device__ __forceinline__ float hl_lstm(const HlW& W, int k0, const float* x, float* zbuf, float* cs, float* hs, float* __restrict__ state, int sdim, int off,
-                                         int row0, int n_rows, int wave, int lane, int tid) {
+template <class WT, class RM>
+__device__ __forceinline__ float hl_lstm(const WT& W, int k0, const float* x, float* zbuf, float* cs, float* hs, float* __restrict__ state, int sdim, int off,
+                                         const RM& R, int wave, int lane, int tid) {
   pol_dense(x, 256, W.a[k0], W.zero, 128, zbuf, 0, wave, lane);                     // x Wx   rows 0..127
   pol_dense(hs, 32, W.a[k0 + 1], W.zero, 128, zbuf + 128 * POL_M, 0, wave, lane);    // h Wh   rows 128..255
   __syncthreads();
-  const int m = tid >> 5, j = tid & 31, r = row0 + m;
+  const int m = tid >> 5, j = tid & 31, r = R.srow(m);
   float zx[4], zh[4];
 #pragma unroll
   for (int g = 0; g < 4; g++) { zx[g] = zbuf[(32 * g + j) * POL_M + m]; zh[g] = zbuf[(128 + 32 * g + j) * POL_M + m]; }
@@ -194,7 +210,7 @@ __device__ __forceinline__ float hl_lstm(const HlW& W, int k0, const float* x, f
   const float h = hl_sigmoid(z[2]) * tanhf((c - mc) * rc * W.a[k0 + 8][j] + W.a[k0 + 7][j]);
   cs[j * POL_M + m] = c;
   hs[j * POL_M + m] = h;
-  if (r < n_rows) { state[(long)r * sdim + off + j] = c; state[(long)r * sdim + off + 32 + j] = h; }
+  if (R.live(m)) { state[(long)r * sdim + off + j] = c; state[(long)r * sdim + off + 32 + j] = h; }
   __syncthreads();
   return h;
 }
@@ -245,15 +261,15 @@ struct HlLds {
 };
 
 // The mid level (EPMC's whole policy; SEPMC's mlc_encoder and llc) with the EPMC checkpoint's array numbers; the SEPMC arrays are OFF = 50
-// further on.  On entry: xs, and the target [3][16] in L.vin.  Writes actions / code of rows < n_rows.
+// further on.  On entry: xs, and the target [3][16] in L.vin.  Writes actions / code of the map's rows.
 // PG: the PPO actor's heads (HlPg): the code and the action sampled when g.sample, neglogp of both when g.neglogp.
-template <int OFF, bool PG = false>
-__device__ __forceinline__ void hl_mid(const HlW& W, HlLds& L, const float* __restrict__ obs, int stride, const uint8_t* __restrict__ reset, float* __restrict__ state,
-                                       int sdim, int soff, float* __restrict__ actions, int32_t* __restrict__ code_out, int row0, int n_rows, int wave, int lane, int tid,
+template <int OFF, bool PG = false, class WT, class RM>
+__device__ __forceinline__ void hl_mid(const WT& W, HlLds& L, const float* __restrict__ obs, int stride, const uint8_t* __restrict__ reset, float* __restrict__ state,
+                                       int sdim, int soff, float* __restrict__ actions, int32_t* __restrict__ code_out, const RM& R, int wave, int lane, int tid,
                                        const HlPg& g = HlPg()) {
   float *b0 = L.big, *b1 = L.big + 256 * POL_M;
-  hl_load_state(state, sdim, soff, reset, row0, n_rows, L.cs, L.hs, tid);
-  hl_percepts(W, OFF + 49, obs, stride, row0, n_rows, L.big, L.feat, 32, tid);                     // usr_cmd_encoder: e2d | e1d | efr at 32..119
+  hl_load_state(state, sdim, soff, reset, R, L.cs, L.hs, tid);
+  hl_percepts(W, OFF + 49, obs, stride, R, L.big, L.feat, 32, tid);                                // usr_cmd_encoder: e2d | e1d | efr at 32..119
   pol_dense(L.vin, 3, W.a[OFF + 73], W.a[OFF + 74], 32, L.feat, 1, wave, lane);                   //                  vec at 0..31
   pol_dense(L.xs, 135, W.a[OFF + 47], W.a[OFF + 48], 64, b1, 1, wave, lane);                      // mlc_encoder prop embed: rows 0..63
   __syncthreads();
@@ -261,7 +277,7 @@ __device__ __forceinline__ void hl_mid(const HlW& W, HlLds& L, const float* __re
   __syncthreads();
   pol_dense(b1, 128, W.a[OFF + 77], W.a[OFF + 78], 256, b0, 1, wave, lane);                      // embed
   __syncthreads();
-  hl_lstm(W, OFF + 79, b0, b1, L.cs, L.hs, state, sdim, soff, row0, n_rows, wave, lane, tid);
+  hl_lstm(W, OFF + 79, b0, b1, L.cs, L.hs, state, sdim, soff, R, wave, lane, tid);
   pol_dense(L.hs, 32, W.a[OFF + 88], W.a[OFF + 89], 256, b0, 0, wave, lane);                     // z logits
   __syncthreads();
   if constexpr (PG) {   // first maximum of logit (+ Gumbel noise when sampling) per row; max and sum of exp of 16 logits for the logsumexp
@@ -273,7 +289,7 @@ __device__ __forceinline__ void hl_mid(const HlW& W, HlLds& L, const float* __re
       for (int blk = 0; blk < 4; blk++) {
         uint32_t w[4] = {0u, 0u, 0u, 0u};
         if (g.sample)
-          philox4x32((uint32_t)(row0 + m) * 64u + (uint32_t)(part * 4 + blk), (uint32_t)g.step, (uint32_t)(g.step >> 32), HL_Z_SALT, (uint32_t)g.seed,
+          philox4x32((uint32_t)R.row(m) * 64u + (uint32_t)(part * 4 + blk), (uint32_t)g.step, (uint32_t)(g.step >> 32), HL_Z_SALT, (uint32_t)g.seed,
                      (uint32_t)(g.seed >> 32), w);
 #pragma unroll
         for (int q = 0; q < 4; q++) {
@@ -305,14 +321,14 @@ __device__ __forceinline__ void hl_mid(const HlW& W, HlLds& L, const float* __re
     for (int p = 1; p < 16; p++)
       if (L.pv[p * POL_M + tid] > bv) { bv = L.pv[p * POL_M + tid]; bi = L.pi[p * POL_M + tid]; }
     L.best[tid] = bi;
-    if (code_out && row0 + tid < n_rows) code_out[row0 + tid] = bi;
+    if (code_out && R.live(tid)) code_out[R.row(tid)] = bi;
     if constexpr (PG) {
-      if (g.neglogp && row0 + tid < n_rows) {                                                   // logsumexp(logits) - logits[code]
+      if (g.neglogp && R.live(tid)) {                                                           // logsumexp(logits) - logits[code]
         float mx = g.pm[tid];
         for (int p = 1; p < 16; p++) mx = fmaxf(mx, g.pm[p * POL_M + tid]);
         float se = 0.0f;
         for (int p = 0; p < 16; p++) se += g.ps[p * POL_M + tid] * expf(g.pm[p * POL_M + tid] - mx);
-        g.neglogp[(long)(row0 + tid) * g.nh + g.nh - 2] = mx + logf(se) - b0[bi * POL_M + tid];
+        g.neglogp[(long)R.row(tid) * g.nh + g.nh - 2] = mx + logf(se) - b0[bi * POL_M + tid];
       }
     }
   }
@@ -333,7 +349,8 @@ __device__ __forceinline__ void hl_mid(const HlW& W, HlLds& L, const float* __re
   __syncthreads();
   if constexpr (PG) {
     if (tid < 64) {     // wavefront 0, lane = group * 16 + row: a = mean + exp(logstd) eps (logstd: array OFF + 101), neglogp summed over the groups
-      const int grp = lane >> 4, m = lane & 15, r = row0 + m;
+      const int grp = lane >> 4, m = lane & 15, r = R.row(m);
+      const bool live = R.live(m);
       float eps[4] = {0.0f, 0.0f, 0.0f, 0.0f}, nl = 0.0f;
       if (grp < 3) {
         if (g.sample) hl_normals4(g.seed, g.step, (uint32_t)r * 3u + (uint32_t)grp, HL_LLC_SALT, eps);
@@ -341,17 +358,17 @@ __device__ __forceinline__ void hl_mid(const HlW& W, HlLds& L, const float* __re
         for (int q = 0; q < 4; q++) {
           const int c = 4 * grp + q;
           const float ls = W.a[OFF + 101][c];
-          if (r < n_rows) actions[(long)r * LLH_ACT_DIM + c] = b1[c * POL_M + m] + expf(ls) * eps[q];
+          if (live) actions[(long)r * LLH_ACT_DIM + c] = b1[c * POL_M + m] + expf(ls) * eps[q];
           nl += 0.5f * eps[q] * eps[q] + ls;
         }
       }
       nl += __shfl(nl, lane + 16) + __shfl(nl, lane + 32);
-      if (g.neglogp && grp == 0 && r < n_rows) g.neglogp[(long)r * g.nh + g.nh - 1] = nl + 0.5f * HL_LOG_2PI * LLH_ACT_DIM;
+      if (g.neglogp && grp == 0 && live) g.neglogp[(long)r * g.nh + g.nh - 1] = nl + 0.5f * HL_LOG_2PI * LLH_ACT_DIM;
     }
   } else {
     for (int i = tid; i < POL_M * LLH_ACT_DIM; i += POL_THREADS) {
       const int m = i / LLH_ACT_DIM, c = i - m * LLH_ACT_DIM;
-      if (row0 + m < n_rows) actions[(long)(row0 + m) * LLH_ACT_DIM + c] = b1[c * POL_M + m];
+      if (R.live(m)) actions[(long)R.row(m) * LLH_ACT_DIM + c] = b1[c * POL_M + m];
     }
   }
 }
@@ -361,29 +378,30 @@ __global__ __launch_bounds__(POL_THREADS) void hl_policy_kernel(HlW W, const flo
                                                                 float* __restrict__ state, float* __restrict__ actions, int32_t* __restrict__ code_out,
                                                                 float* __restrict__ heading_out, int n_rows) {
   __shared__ HlLds L;
-  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, row0 = blockIdx.x * POL_M;
+  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+  const HlDense R = {(int)blockIdx.x * POL_M, n_rows};
   for (int i = tid; i < POL_M * 135; i += POL_THREADS) {        // rms normalisation + clip to +-5 (layers.py:55)
-    const int m = i / 135, k = i - m * 135, r = row0 + m;
-    const float x = r < n_rows ? obs[(long)r * stride + k] : 0.0f;
+    const int m = i / 135, k = i - m * 135, r = R.row(m);
+    const float x = R.live(m) ? obs[(long)r * stride + k] : 0.0f;
     L.xs[k * POL_M + m] = fminf(fmaxf((x - W.a[0][k]) / (W.a[1][k] + 1e-8f), -5.0f), 5.0f);
   }
   if (KIND == LLH_EPMC) {
     if (tid < 3 * POL_M) {                                       // target (913..915)
-      const int k = tid >> 4, m = tid & 15, r = row0 + m;
-      L.vin[k * POL_M + m] = r < n_rows ? obs[(long)r * stride + 913 + k] : 0.0f;
+      const int k = tid >> 4, m = tid & 15, r = R.row(m);
+      L.vin[k * POL_M + m] = R.live(m) ? obs[(long)r * stride + 913 + k] : 0.0f;
     }
     __syncthreads();
-    hl_mid<0>(W, L, obs, stride, reset, state, 64, 0, actions, code_out, row0, n_rows, wave, lane, tid);
+    hl_mid<0>(W, L, obs, stride, reset, state, 64, 0, actions, code_out, R, wave, lane, tid);
   } else {
     float *b0 = L.big, *b1 = L.big + 256 * POL_M;
     if (tid < 29 * POL_M) {                                      // percept_vec 913..917 | oppo_info 918..932 | flag_info 948..954 | with_flag 962..963
-      const int k = tid >> 4, m = tid & 15, r = row0 + m;
+      const int k = tid >> 4, m = tid & 15, r = R.row(m);
       const int col = k < 20 ? 913 + k : (k < 27 ? 948 + k - 20 : 962 + k - 27);
-      L.vin[k * POL_M + m] = r < n_rows ? obs[(long)r * stride + col] : 0.0f;
+      L.vin[k * POL_M + m] = R.live(m) ? obs[(long)r * stride + col] : 0.0f;
     }
-    hl_load_state(state, 128, 0, reset, row0, n_rows, L.cs, L.hs, tid);
+    hl_load_state(state, 128, 0, reset, R, L.cs, L.hs, tid);
     __syncthreads();
-    hl_percepts(W, 53, obs, stride, row0, n_rows, L.big, L.feat, 0, tid);               // hlc_encoder percepts -> feat 0..87
+    hl_percepts(W, 53, obs, stride, R, L.big, L.feat, 0, tid);                        // hlc_encoder percepts -> feat 0..87
     pol_dense(L.xs, 135, W.a[51], W.a[52], 64, b1, 1, wave, lane);                      // embed input: prop 0..63 | percepts 64..127 | vector 128..191
     pol_dense(L.feat, 88, W.a[77], W.a[78], 64, b1 + 64 * POL_M, 1, (wave + 4) & 7, lane);
     pol_dense(L.vin, 29, W.a[79], W.a[80], 64, b0, 1, wave, lane);
@@ -392,17 +410,17 @@ __global__ __launch_bounds__(POL_THREADS) void hl_policy_kernel(HlW W, const flo
     __syncthreads();
     pol_dense(b1, 192, W.a[83], W.a[84], 256, b0, 1, wave, lane);
     __syncthreads();
-    const float h = hl_lstm(W, 85, b0, b1, L.cs, L.hs, state, 128, 0, row0, n_rows, wave, lane, tid);
-    const int m = tid >> 5, j = tid & 31, r = row0 + m;
+    const float h = hl_lstm(W, 85, b0, b1, L.cs, L.hs, state, 128, 0, R, wave, lane, tid);
+    const int m = tid >> 5, j = tid & 31, r = R.row(m);
     const float hd = fminf(fmaxf(hl_sum32(h * W.a[94][j]) + W.a[95][0], -HL_PI), HL_PI);   // the Gaussian head's mean, clipped to +-pi
     if (j == 0) {                                                                       // the mid level's target: cos, sin, control_spd
       L.vin[0 * POL_M + m] = cosf(hd);
       L.vin[1 * POL_M + m] = sinf(hd);
-      L.vin[2 * POL_M + m] = r < n_rows ? obs[(long)r * stride + 964] : 0.0f;
-      if (heading_out && r < n_rows) heading_out[r] = hd;
+      L.vin[2 * POL_M + m] = R.live(m) ? obs[(long)r * stride + 964] : 0.0f;
+      if (heading_out && R.live(m)) heading_out[r] = hd;
     }
     __syncthreads();
-    hl_mid<50>(W, L, obs, stride, reset, state, 128, 64, actions, code_out, row0, n_rows, wave, lane, tid);
+    hl_mid<50>(W, L, obs, stride, reset, state, 128, 64, actions, code_out, R, wave, lane, tid);
   }
 }
 
@@ -423,32 +441,32 @@ struct HlPgLds {
 };
 
 // The value branch (epmc_net.py:226-244, sepmc_net.py:271-292) of 16 rows on the checkpoint's arrays 2..46 (EPMC) / 2..50 (SEPMC); its LSTM
-// state [max_rows][64] (c | h) in vstate, zeroed by reset like the policy's.  value[r] <- the value of rows r < n_rows.
-template <int KIND>
-__device__ __forceinline__ void hl_value(const HlW& W, HlVLds& V, const float* __restrict__ obs, int stride, const uint8_t* __restrict__ reset,
-                                         float* __restrict__ vstate, float* __restrict__ value, int row0, int n_rows, int wave, int lane, int tid) {
+// state [max_rows][64] (c | h) in vstate, zeroed by reset like the policy's.  value[R.srow(m)] <- the value of the map's rows.
+template <int KIND, class WT, class RM>
+__device__ __forceinline__ void hl_value(const WT& W, HlVLds& V, const float* __restrict__ obs, int stride, const uint8_t* __restrict__ reset,
+                                         float* __restrict__ vstate, float* __restrict__ value, const RM& R, int wave, int lane, int tid) {
   float *a = V.a, *b = V.b, *xs = V.b + 120 * POL_M;
   for (int i = tid; i < POL_M * 135; i += POL_THREADS) {        // the policy's rms normalisation (arrays 0, 1)
-    const int m = i / 135, k = i - m * 135, r = row0 + m;
-    const float x = r < n_rows ? obs[(long)r * stride + k] : 0.0f;
+    const int m = i / 135, k = i - m * 135, r = R.row(m);
+    const float x = R.live(m) ? obs[(long)r * stride + k] : 0.0f;
     xs[k * POL_M + m] = fminf(fmaxf((x - W.a[0][k]) / (W.a[1][k] + 1e-8f), -5.0f), 5.0f);
   }
   if (KIND == LLH_EPMC) {
     if (tid < 3 * POL_M) {                                       // target (913..915)
-      const int k = tid >> 4, m = tid & 15, r = row0 + m;
-      V.vin[k * POL_M + m] = r < n_rows ? obs[(long)r * stride + 913 + k] : 0.0f;
+      const int k = tid >> 4, m = tid & 15, r = R.row(m);
+      V.vin[k * POL_M + m] = R.live(m) ? obs[(long)r * stride + 913 + k] : 0.0f;
     }
   } else if (tid < 29 * POL_M) {                                 // percept_vec 913..917 | oppo_info_cheat 933..947 | flag_info_cheat 955..961 | with_flag 962..963
-    const int k = tid >> 4, m = tid & 15, r = row0 + m;
+    const int k = tid >> 4, m = tid & 15, r = R.row(m);
     const int col = k < 5 ? 913 + k : (k < 20 ? 933 + k - 5 : (k < 27 ? 955 + k - 20 : 962 + k - 27));
-    V.vin[k * POL_M + m] = r < n_rows ? obs[(long)r * stride + col] : 0.0f;
+    V.vin[k * POL_M + m] = R.live(m) ? obs[(long)r * stride + col] : 0.0f;
   }
-  hl_load_state(vstate, 64, 0, reset, row0, n_rows, V.cs, V.hs, tid);
+  hl_load_state(vstate, 64, 0, reset, R, V.cs, V.hs, tid);
   __syncthreads();
   float h;
   int kv;
   if (KIND == LLH_EPMC) {
-    hl_percepts(W, 4, obs, stride, row0, n_rows, a, b, 32, tid);                     // usr_cmd_encoder: e2d | e1d | efr -> b rows 32..119
+    hl_percepts(W, 4, obs, stride, R, a, b, 32, tid);                              // usr_cmd_encoder: e2d | e1d | efr -> b rows 32..119
     pol_dense(V.vin, 3, W.a[28], W.a[29], 32, b, 1, wave, lane);                     //                  vec -> b rows 0..31
     pol_dense(xs, 135, W.a[2], W.a[3], 128, a + 128 * POL_M, 2, wave, lane);         // fc1, tanh -> a rows 128..255
     __syncthreads();
@@ -458,10 +476,10 @@ __device__ __forceinline__ void hl_value(const HlW& W, HlVLds& V, const float* _
     __syncthreads();
     pol_dense(a + 128 * POL_M, 256, W.a[34], W.a[35], 256, b, 2, wave, lane);        // fc3 of [fc1 | fc2], tanh -> b
     __syncthreads();
-    h = hl_lstm(W, 36, b, a, V.cs, V.hs, vstate, 64, 0, row0, n_rows, wave, lane, tid);
+    h = hl_lstm(W, 36, b, a, V.cs, V.hs, vstate, 64, 0, R, wave, lane, tid);
     kv = 45;
   } else {
-    hl_percepts(W, 4, obs, stride, row0, n_rows, a, b, 0, tid);                      // mlc_usr_cmd_encoder: e2d | e1d | efr -> b rows 0..87
+    hl_percepts(W, 4, obs, stride, R, a, b, 0, tid);                               // mlc_usr_cmd_encoder: e2d | e1d | efr -> b rows 0..87
     pol_dense(b, 88, W.a[28], W.a[29], 64, a, 1, wave, lane);                        // bottleneck -> a rows 0..63
     pol_dense(V.vin, 29, W.a[32], W.a[33], 64, a + 64 * POL_M, 1, (wave + 4) & 7, lane);   // hlc_usr_cmd_encoder 1 -> a rows 64..127
     pol_dense(xs, 135, W.a[2], W.a[3], 128, a + 128 * POL_M, 2, wave, lane);         // fc1, tanh -> a rows 128..255
@@ -473,53 +491,45 @@ __device__ __forceinline__ void hl_value(const HlW& W, HlVLds& V, const float* _
     __syncthreads();
     pol_dense(a + 128 * POL_M, 384, W.a[38], W.a[39], 256, b, 2, wave, lane);        // fc4 of [fc1 | fc2 | fc3], tanh -> b
     __syncthreads();
-    h = hl_lstm(W, 40, b, a, V.cs, V.hs, vstate, 64, 0, row0, n_rows, wave, lane, tid);
+    h = hl_lstm(W, 40, b, a, V.cs, V.hs, vstate, 64, 0, R, wave, lane, tid);
     kv = 49;
   }
-  const int m = tid >> 5, j = tid & 31, r = row0 + m;
+  const int m = tid >> 5, j = tid & 31;
   const float v = hl_sum32(h * W.a[kv][j]) + W.a[kv + 1][0];                         // value dense, linear
-  if (j == 0 && r < n_rows) value[r] = v;
+  if (j == 0 && R.live(m)) value[R.srow(m)] = v;
 }
 
-// The PPO actor launch: blockIdx.y 0 = the policy of hl_policy_kernel with its heads sampled / scored (HlPg); blockIdx.y 1 (launched only
-// when a value is asked for) = the value branch of the same rows.  Neither waits on the other.
-template <int KIND>
-__global__ __launch_bounds__(POL_THREADS) void hl_policy_pg_kernel(HlW W, const float* __restrict__ obs, int stride, const uint8_t* __restrict__ reset,
-                                                                   float* __restrict__ state, float* __restrict__ vstate, float* __restrict__ actions,
-                                                                   int32_t* __restrict__ code_out, float* __restrict__ heading_out, float* __restrict__ neglogp,
-                                                                   float* __restrict__ value, uint64_t seed, uint64_t step, int sample, int n_rows) {
-  __shared__ HlPgLds S;
-  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, row0 = blockIdx.x * POL_M;
-  if (blockIdx.y == 1) {
-    hl_value<KIND>(W, S.u.V, obs, stride, reset, vstate, value, row0, n_rows, wave, lane, tid);
-    return;
-  }
+// The policy of hl_policy_kernel with its heads sampled / scored (HlPg) for the 16 rows of R: what blockIdx.y 0 of the PPO actor launch runs.
+template <int KIND, class WT, class RM>
+__device__ __forceinline__ void hl_pg_policy(const WT& W, const RM& R, HlPgLds& S, const float* __restrict__ obs, int stride, const uint8_t* __restrict__ reset,
+                                             float* __restrict__ state, float* __restrict__ actions, int32_t* __restrict__ code_out, float* __restrict__ heading_out,
+                                             float* __restrict__ neglogp, uint64_t seed, uint64_t step, int sample, int wave, int lane, int tid) {
   HlLds& L = S.u.P;
   HlPg g;
   g.seed = seed; g.step = step; g.sample = sample; g.neglogp = neglogp; g.pm = S.pm; g.ps = S.ps;
   g.nh = KIND == LLH_EPMC ? LLH_EPMC_N_HEADS : LLH_SEPMC_N_HEADS;
   for (int i = tid; i < POL_M * 135; i += POL_THREADS) {        // rms normalisation + clip to +-5 (layers.py:55)
-    const int m = i / 135, k = i - m * 135, r = row0 + m;
-    const float x = r < n_rows ? obs[(long)r * stride + k] : 0.0f;
+    const int m = i / 135, k = i - m * 135, r = R.row(m);
+    const float x = R.live(m) ? obs[(long)r * stride + k] : 0.0f;
     L.xs[k * POL_M + m] = fminf(fmaxf((x - W.a[0][k]) / (W.a[1][k] + 1e-8f), -5.0f), 5.0f);
   }
   if (KIND == LLH_EPMC) {
     if (tid < 3 * POL_M) {                                       // target (913..915)
-      const int k = tid >> 4, m = tid & 15, r = row0 + m;
-      L.vin[k * POL_M + m] = r < n_rows ? obs[(long)r * stride + 913 + k] : 0.0f;
+      const int k = tid >> 4, m = tid & 15, r = R.row(m);
+      L.vin[k * POL_M + m] = R.live(m) ? obs[(long)r * stride + 913 + k] : 0.0f;
     }
     __syncthreads();
-    hl_mid<0, true>(W, L, obs, stride, reset, state, 64, 0, actions, code_out, row0, n_rows, wave, lane, tid, g);
+    hl_mid<0, true>(W, L, obs, stride, reset, state, 64, 0, actions, code_out, R, wave, lane, tid, g);
   } else {
     float *b0 = L.big, *b1 = L.big + 256 * POL_M;
     if (tid < 29 * POL_M) {                                      // percept_vec 913..917 | oppo_info 918..932 | flag_info 948..954 | with_flag 962..963
-      const int k = tid >> 4, m = tid & 15, r = row0 + m;
+      const int k = tid >> 4, m = tid & 15, r = R.row(m);
       const int col = k < 20 ? 913 + k : (k < 27 ? 948 + k - 20 : 962 + k - 27);
-      L.vin[k * POL_M + m] = r < n_rows ? obs[(long)r * stride + col] : 0.0f;
+      L.vin[k * POL_M + m] = R.live(m) ? obs[(long)r * stride + col] : 0.0f;
     }
-    hl_load_state(state, 128, 0, reset, row0, n_rows, L.cs, L.hs, tid);
+    hl_load_state(state, 128, 0, reset, R, L.cs, L.hs, tid);
     __syncthreads();
-    hl_percepts(W, 53, obs, stride, row0, n_rows, L.big, L.feat, 0, tid);
+    hl_percepts(W, 53, obs, stride, R, L.big, L.feat, 0, tid);
     pol_dense(L.xs, 135, W.a[51], W.a[52], 64, b1, 1, wave, lane);
     pol_dense(L.feat, 88, W.a[77], W.a[78], 64, b1 + 64 * POL_M, 1, (wave + 4) & 7, lane);
     pol_dense(L.vin, 29, W.a[79], W.a[80], 64, b0, 1, wave, lane);
@@ -528,8 +538,8 @@ __global__ __launch_bounds__(POL_THREADS) void hl_policy_pg_kernel(HlW W, const 
     __syncthreads();
     pol_dense(b1, 192, W.a[83], W.a[84], 256, b0, 1, wave, lane);
     __syncthreads();
-    const float h = hl_lstm(W, 85, b0, b1, L.cs, L.hs, state, 128, 0, row0, n_rows, wave, lane, tid);
-    const int m = tid >> 5, j = tid & 31, r = row0 + m;
+    const float h = hl_lstm(W, 85, b0, b1, L.cs, L.hs, state, 128, 0, R, wave, lane, tid);
+    const int m = tid >> 5, j = tid & 31, r = R.row(m);
     const float mu = fminf(fmaxf(hl_sum32(h * W.a[94][j]) + W.a[95][0], -HL_PI), HL_PI);   // the Gaussian head's mean, clipped to +-pi
     if (j == 0) {   // heading = mu + exp(a96) eps, not clipped (a96, 'logvar' in sepmc_net.py, is the DiagGaussian's logstd half); the mid level's target
       float eps[4] = {0.0f, 0.0f, 0.0f, 0.0f};
@@ -537,13 +547,30 @@ __global__ __launch_bounds__(POL_THREADS) void hl_policy_pg_kernel(HlW W, const 
       const float ls = W.a[96][0], hd = mu + expf(ls) * eps[0];
       L.vin[0 * POL_M + m] = cosf(hd);
       L.vin[1 * POL_M + m] = sinf(hd);
-      L.vin[2 * POL_M + m] = r < n_rows ? obs[(long)r * stride + 964] : 0.0f;
-      if (heading_out && r < n_rows) heading_out[r] = hd;
-      if (neglogp && r < n_rows) neglogp[(long)r * LLH_SEPMC_N_HEADS] = 0.5f * eps[0] * eps[0] + 0.5f * HL_LOG_2PI + ls;
+      L.vin[2 * POL_M + m] = R.live(m) ? obs[(long)r * stride + 964] : 0.0f;
+      if (heading_out && R.live(m)) heading_out[r] = hd;
+      if (neglogp && R.live(m)) neglogp[(long)r * LLH_SEPMC_N_HEADS] = 0.5f * eps[0] * eps[0] + 0.5f * HL_LOG_2PI + ls;
     }
     __syncthreads();
-    hl_mid<50, true>(W, L, obs, stride, reset, state, 128, 64, actions, code_out, row0, n_rows, wave, lane, tid, g);
+    hl_mid<50, true>(W, L, obs, stride, reset, state, 128, 64, actions, code_out, R, wave, lane, tid, g);
   }
+}
+
+// The PPO actor launch: blockIdx.y 0 = hl_pg_policy; blockIdx.y 1 (launched only when a value is asked for) = the value branch of the same rows.
+// Neither waits on the other.
+template <int KIND>
+__global__ __launch_bounds__(POL_THREADS) void hl_policy_pg_kernel(HlW W, const float* __restrict__ obs, int stride, const uint8_t* __restrict__ reset,
+                                                                   float* __restrict__ state, float* __restrict__ vstate, float* __restrict__ actions,
+                                                                   int32_t* __restrict__ code_out, float* __restrict__ heading_out, float* __restrict__ neglogp,
+                                                                   float* __restrict__ value, uint64_t seed, uint64_t step, int sample, int n_rows) {
+  __shared__ HlPgLds S;
+  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+  const HlDense R = {(int)blockIdx.x * POL_M, n_rows};
+  if (blockIdx.y == 1) {
+    hl_value<KIND>(W, S.u.V, obs, stride, reset, vstate, value, R, wave, lane, tid);
+    return;
+  }
+  hl_pg_policy<KIND>(W, R, S, obs, stride, reset, state, actions, code_out, heading_out, neglogp, seed, step, sample, wave, lane, tid);
 }
 
 struct ll_hl_policy {
@@ -551,6 +578,9 @@ struct ll_hl_policy {
   float *d_w, *d_state;
   float *d_vw, *d_vstate;        // the value branch (ll_hl_policy_attach_value) and its state [max_rows][64]; null until attached
   HlW W;
+  float* h_stage;                // pinned [n_floats + n_vf_floats]: what ll_hl_policy_set_weights uploads from; null until its first call
+  hipEvent_t up_ev;              // the last upload from h_stage
+  bool up_pending;
   bool timing;
   std::vector<std::pair<hipEvent_t, hipEvent_t>> evs;
   size_t ev_used;
@@ -601,6 +631,7 @@ int ll_hl_policy_create(int kind, const float* h_weights, int n_floats, int max_
   ll_hl_policy* p = new ll_hl_policy();
   p->kind = kind; p->device = device; p->max_rows = max_rows; p->state_dim = kind == LLH_EPMC ? 64 : 128;
   p->timing = false; p->ev_used = 0; p->d_w = nullptr; p->d_state = nullptr; p->d_vw = nullptr; p->d_vstate = nullptr;
+  p->h_stage = nullptr; p->up_ev = nullptr; p->up_pending = false;
   const size_t sbytes = (size_t)max_rows * p->state_dim * sizeof(float);
   if (hipMalloc(&p->d_w, ((size_t)want + 256) * sizeof(float)) != hipSuccess || hipMalloc(&p->d_state, sbytes) != hipSuccess) {
     if (p->d_w) (void)hipFree(p->d_w);
@@ -634,6 +665,8 @@ int ll_hl_policy_destroy(ll_hl_policy* p) {
     (void)hipFree(p->d_state);
     if (p->d_vw) (void)hipFree(p->d_vw);
     if (p->d_vstate) (void)hipFree(p->d_vstate);
+    if (p->h_stage) { (void)hipDeviceSynchronize(); (void)hipHostFree(p->h_stage); }
+    if (p->up_ev) (void)hipEventDestroy(p->up_ev);
     delete p;
   }
   LL_CATCH
@@ -745,6 +778,40 @@ int ll_hl_policy_act_pg(ll_hl_policy* p, const float* d_obs, int obs_stride, con
                        d_neglogp, d_value, seed, step, sample, n_rows);
   HIPCHK(hipGetLastError());
   if (ev) HIPCHK(hipEventRecord(ev->second, st));
+  LL_CATCH
+}
+
+int ll_hl_policy_set_weights(ll_hl_policy* p, const float* h_weights, int n_floats, const float* h_vf_weights, int n_vf_floats, void* hip_stream) {
+  LL_TRY
+  hl_check(p);
+  LL_CHECK(h_weights, "null argument");
+  const bool ep = p->kind == LLH_EPMC;
+  const int want = ep ? LLH_EPMC_N_FLOATS : LLH_SEPMC_N_FLOATS, vwant = ep ? LLH_EPMC_VF_N_FLOATS : LLH_SEPMC_VF_N_FLOATS;
+  LL_CHECK(n_floats == want, "weights: not the float count ll_hl_policy_create takes for this kind");
+  if (p->d_vw) {
+    LL_CHECK(h_vf_weights, "h_vf_weights: the policy has a value branch attached, a new model replaces both");
+    LL_CHECK(n_vf_floats == vwant, "value weights: not the float count ll_hl_policy_attach_value takes for this kind");
+  } else {
+    LL_CHECK(!h_vf_weights, "h_vf_weights: no value branch attached (ll_hl_policy_attach_value)");
+  }
+  HIPCHK(hipSetDevice(p->device));
+  hipStream_t st = (hipStream_t)hip_stream;
+  if (!p->h_stage) {
+    if (hipHostMalloc((void**)&p->h_stage, ((size_t)want + vwant) * sizeof(float), hipHostMallocDefault) != hipSuccess) {
+      p->h_stage = nullptr;
+      throw PmcError(LL_ENOMEM, "hipHostMalloc of the weight staging buffer failed");
+    }
+    HIPCHK(hipEventCreateWithFlags(&p->up_ev, hipEventDisableTiming));
+  }
+  if (p->up_pending) HIPCHK(hipEventSynchronize(p->up_ev));      // the staging buffer is free once the previous upload has left it
+  memcpy(p->h_stage, h_weights, (size_t)want * sizeof(float));
+  HIPCHK(hipMemcpyAsync(p->d_w, p->h_stage, (size_t)want * sizeof(float), hipMemcpyHostToDevice, st));
+  if (h_vf_weights) {
+    memcpy(p->h_stage + want, h_vf_weights, (size_t)vwant * sizeof(float));
+    HIPCHK(hipMemcpyAsync(p->d_vw, p->h_stage + want, (size_t)vwant * sizeof(float), hipMemcpyHostToDevice, st));
+  }
+  HIPCHK(hipEventRecord(p->up_ev, st));
+  p->up_pending = true;
   LL_CATCH
 }
 

@@ -33,42 +33,45 @@ struct HluArgs {
   int n_rows, L;
 };
 
-// column j of S for `row`: vf c|h, pi (no LSTM: zeros), z c|h, and SEPMC's hlc c|h last
+// column j of S for recorded row `row`, engine row `src`: vf c|h, pi (no LSTM: zeros), z c|h, and SEPMC's hlc c|h last
 template <int KIND>
-__device__ __forceinline__ float hlu_state_col(const HluArgs& a, int row, int j) {
+__device__ __forceinline__ float hlu_state_col(const HluArgs& a, int row, int src, int j) {
   if (j < 64) return a.vstate[(size_t)row * 64 + j];
   if (j < 128) return 0.0f;
-  if (KIND == LLH_EPMC) return a.state[(size_t)row * 64 + (j - 128)];
-  return j < 192 ? a.state[(size_t)row * 128 + 64 + (j - 128)] : a.state[(size_t)row * 128 + (j - 192)];
+  if (KIND == LLH_EPMC) return a.state[(size_t)src * 64 + (j - 128)];
+  return j < 192 ? a.state[(size_t)src * 128 + 64 + (j - 128)] : a.state[(size_t)src * 128 + (j - 192)];
 }
 
 // post_slot / pre_slot: the time step inside post_buf / pre_buf, -1: that half of the launch is not wanted.  One wave per row; a lane issues every
 // load of its share of the row before its first store, so a row costs one round of loads and one of stores.
-template <int KIND>
+// RSTEP: recorded row `row` is the engine's (and the policy's) row RSTEP * row; the value and its state are indexed by `row` itself.  1: every row
+// (ll_hl_unroll); 2: robot 0 of every arena (hl_league.inc).
+template <int KIND, int RSTEP = 1>
 __global__ __launch_bounds__(HLU_THREADS) void hl_unroll_record_kernel(HluArgs a, int post_buf, int post_slot, int pre_buf, int pre_slot) {
   typedef HluRow<KIND> Y;
   const int lane = threadIdx.x & 63, row = blockIdx.x * HLU_ROWS + (threadIdx.x >> 6);
   if (row >= a.n_rows) return;
-  const bool dn = a.done[row] != 0;
+  const int src = row * RSTEP;
+  const bool dn = a.done[src] != 0;
   if (post_slot >= 0) {
     float* dst = a.base + (((size_t)post_buf * a.n_rows + row) * a.L + post_slot) * Y::RF;
     const int k = lane;
     if (k < Y::A_DIM) {
       const int j = KIND == LLH_SEPMC ? k - 1 : k;                  // -1: the heading
-      dst[Y::A_OFF + k] = j < 0 ? a.heading[row] : j == 0 ? (float)a.code[row] : a.actions[(size_t)row * 12 + (j - 1)];
+      dst[Y::A_OFF + k] = j < 0 ? a.heading[src] : j == 0 ? (float)a.code[src] : a.actions[(size_t)src * 12 + (j - 1)];
     } else if (k < Y::A_DIM + Y::NH) {
-      dst[Y::A_OFF + k] = a.neglogp[(size_t)row * Y::NH + (k - Y::A_DIM)];
+      dst[Y::A_OFF + k] = a.neglogp[(size_t)src * Y::NH + (k - Y::A_DIM)];
     } else if (k == Y::A_DIM + Y::NH + 1) {                          // (R, one column before, is ll_hl_unroll_finish's)
       dst[Y::V_OFF] = a.value[row];
     } else if (k == Y::A_DIM + Y::NH + 2) {
-      dst[Y::RW_OFF] = a.reward[row];
+      dst[Y::RW_OFF] = a.reward[src];
     } else if (k == Y::A_DIM + Y::NH + 3) {
       dst[Y::DC_OFF] = dn ? 0.0f : 1.0f;
     }
   }
   if (pre_slot >= 0) {
     float* dst = a.base + (((size_t)pre_buf * a.n_rows + row) * a.L + pre_slot) * Y::RF;        // 16-byte aligned: RF is a multiple of 4
-    const float* x = a.obs + (size_t)row * Y::OD;
+    const float* x = a.obs + (size_t)src * Y::OD;
     // X in 16-byte stores; 16-byte loads where the source row is aligned too (every EPMC row, every fourth SEPMC row)
     constexpr int XQ = Y::OD / 4, NX = (XQ + 63) / 64;
     const bool aligned = (reinterpret_cast<uintptr_t>(x) & 15) == 0;
@@ -87,7 +90,7 @@ __global__ __launch_bounds__(HLU_THREADS) void hl_unroll_record_kernel(HluArgs a
     const float m = (dn && pre_slot > 0) ? 1.0f : 0.0f;
     auto col = [&](int c) -> float {
       const int j = c - Y::S_OFF;
-      if (j < Y::S_DIM) return dn ? 0.0f : hlu_state_col<KIND>(a, row, j);
+      if (j < Y::S_DIM) return dn ? 0.0f : hlu_state_col<KIND>(a, row, src, j);
       return j == Y::S_DIM ? m : 0.0f;
     };
     constexpr int HEAD = (4 - Y::S_OFF % 4) % 4, Q0 = Y::S_OFF + HEAD, TQ = (Y::RF - Q0) / 4;
@@ -137,7 +140,14 @@ struct ll_hl_unroll {
   uint64_t steps;                   // control steps since create
 };
 
-static void hlu_fill_layout(const ll_hl_unroll* r, ll_hl_unroll_layout_t* o) {
+// the ring [nbuf][n_rows][L][RF] of a recorder: what ll_hl_unroll and ll_hl_league (hl_league.inc) share
+struct HluRing {
+  int kind, n_rows, L, nbuf, RF;
+  float* d_base;
+  size_t n_bytes;
+};
+
+static void hlu_fill_layout(const HluRing* r, ll_hl_unroll_layout_t* o) {
   const bool ep = r->kind == LLH_EPMC;
   typedef HluRow<LLH_EPMC> E;
   typedef HluRow<LLH_SEPMC> S;
@@ -212,6 +222,32 @@ static void hlu_launch_record(ll_hl_unroll* r, hipStream_t st, int64_t post_step
   HIPCHK(hipGetLastError());
 }
 
+// ll_hl_unroll_finish / ll_hl_league_finish on ring r after `steps` recorded steps, on the engine's stream
+static void hlu_finish(ENGINE* base, const HluRing* r, uint64_t steps, const char* who, int buffer, float gamma, float lam, const float* d_bootstrap_value) {
+  LL_CHECK(buffer >= 0 && buffer < r->nbuf, "buffer index out of range");
+  const uint64_t L = (uint64_t)r->L;
+  const float* boot = d_bootstrap_value;
+  size_t bstride = 1;
+  if (!boot) {
+    // the newest complete unroll k of this block; its V_T is V of time step 0 of unroll k + 1, which the post-step record of step (k + 1) L writes
+    const int64_t done_unrolls = (int64_t)(steps / L);
+    int64_t k = done_unrolls - 1;
+    while (k >= 0 && k % r->nbuf != buffer) k--;
+    if (k < 0) throw PmcError(LL_ESTATE, std::string(who) + ": block " + std::to_string(buffer) + " holds no complete unroll yet; pass d_bootstrap_value to finish it anyway");
+    if (steps < (uint64_t)(k + 1) * L + 1)
+      throw PmcError(LL_ESTATE, std::string(who) + ": the first step of the next unroll, whose value bootstraps this one, has not run; step once more or pass "
+                                "d_bootstrap_value");
+    const int nb = (int)((k + 1) % r->nbuf);
+    boot = r->d_base + (size_t)nb * r->n_rows * r->L * r->RF + (r->kind == LLH_EPMC ? HluRow<LLH_EPMC>::V_OFF : HluRow<LLH_SEPMC>::V_OFF);
+    bstride = (size_t)r->L * r->RF;
+  }
+  base->bk.use();
+  hipStream_t st = (hipStream_t)base->bk.stream_handle();
+  hipLaunchKernelGGL(hl_unroll_gae_kernel, dim3((r->n_rows + 255) / 256), dim3(256), 0, st, r->d_base + (size_t)buffer * r->n_rows * r->L * r->RF, r->n_rows, r->L,
+                     r->RF, r->kind == LLH_EPMC ? HluRow<LLH_EPMC>::R_OFF : HluRow<LLH_SEPMC>::R_OFF, gamma, lam, boot, bstride);
+  HIPCHK(hipGetLastError());
+}
+
 extern "C" {
 
 int ll_hl_unroll_create_epmc(ll_epmc_engine* e, ll_hl_policy* p, int unroll_length, int n_buffers, ll_hl_unroll** out) {
@@ -237,7 +273,8 @@ int ll_hl_unroll_destroy(ll_hl_unroll* r) {
 int ll_hl_unroll_layout(ll_hl_unroll* r, ll_hl_unroll_layout_t* out) {
   LL_TRY
   LL_CHECK(r && out, "null argument");
-  hlu_fill_layout(r, out);
+  const HluRing ring = {r->kind, r->n_rows, r->L, r->nbuf, r->RF, r->d_base, r->n_bytes};
+  hlu_fill_layout(&ring, out);
   LL_CATCH
 }
 
@@ -277,28 +314,8 @@ int ll_hl_unroll_position(ll_hl_unroll* r, int64_t* unroll_index, int* time_step
 int ll_hl_unroll_finish(ll_hl_unroll* r, int buffer, float gamma, float lam, const float* d_bootstrap_value) {
   LL_TRY
   LL_CHECK(r, "null recorder");
-  LL_CHECK(buffer >= 0 && buffer < r->nbuf, "buffer index out of range");
-  const uint64_t L = (uint64_t)r->L;
-  const float* boot = d_bootstrap_value;
-  size_t bstride = 1;
-  if (!boot) {
-    // the newest complete unroll k of this block; its V_T is V of time step 0 of unroll k + 1, which the post-step record of step (k + 1) L writes
-    const int64_t done_unrolls = (int64_t)(r->steps / L);
-    int64_t k = done_unrolls - 1;
-    while (k >= 0 && k % r->nbuf != buffer) k--;
-    if (k < 0) throw PmcError(LL_ESTATE, "ll_hl_unroll_finish: block " + std::to_string(buffer) + " holds no complete unroll yet; pass d_bootstrap_value to finish it anyway");
-    if (r->steps < (uint64_t)(k + 1) * L + 1)
-      throw PmcError(LL_ESTATE, "ll_hl_unroll_finish: the first step of the next unroll, whose value bootstraps this one, has not run; step once more or pass "
-                                "d_bootstrap_value");
-    const int nb = (int)((k + 1) % r->nbuf);
-    boot = r->d_base + (size_t)nb * r->n_rows * r->L * r->RF + (r->kind == LLH_EPMC ? HluRow<LLH_EPMC>::V_OFF : HluRow<LLH_SEPMC>::V_OFF);
-    bstride = (size_t)r->L * r->RF;
-  }
-  r->base->bk.use();
-  hipStream_t st = (hipStream_t)r->base->bk.stream_handle();
-  hipLaunchKernelGGL(hl_unroll_gae_kernel, dim3((r->n_rows + 255) / 256), dim3(256), 0, st, r->d_base + (size_t)buffer * r->n_rows * r->L * r->RF, r->n_rows, r->L,
-                     r->RF, r->kind == LLH_EPMC ? HluRow<LLH_EPMC>::R_OFF : HluRow<LLH_SEPMC>::R_OFF, gamma, lam, boot, bstride);
-  HIPCHK(hipGetLastError());
+  const HluRing ring = {r->kind, r->n_rows, r->L, r->nbuf, r->RF, r->d_base, r->n_bytes};
+  hlu_finish(r->base, &ring, r->steps, "ll_hl_unroll_finish", buffer, gamma, lam, d_bootstrap_value);
   LL_CATCH
 }
 

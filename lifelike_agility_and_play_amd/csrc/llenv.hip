@@ -708,5 +708,6 @@ typedef SepmcEngine<HipBackend> SEPMC_ENGINE;
 #include "pmc_policy.inc"
 #include "hl_policy.inc"
 #include "hl_unroll.inc"
+#include "hl_league.inc"
 #include "xfer_capi.inc"
 #endif  // LL_KERNELS_ONLY

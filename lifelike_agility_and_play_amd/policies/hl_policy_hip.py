@@ -43,6 +43,7 @@ _SIGS = {
                                       C.c_uint64, C.c_uint64, C.c_int, C.c_int, C.c_void_p]),
     'll_hl_policy_get_value_state': (C.c_int, [C.c_void_p, C.c_void_p]),
     'll_hl_policy_set_value_state': (C.c_int, [C.c_void_p, C.c_void_p]),
+    'll_hl_policy_set_weights': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p]),
     'll_hl_policy_enable_timing': (C.c_int, [C.c_void_p, C.c_int]),
     'll_hl_policy_time_ms': (C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_int)]),
 }
@@ -103,6 +104,16 @@ class _HipHlPolicy(object):
         w = pack_value_weights(self.KIND, npz_path) if weights is None else np.ascontiguousarray(weights, dtype=np.float32)
         self._chk(self.lib.ll_hl_policy_attach_value(self.h, w.ctypes.data_as(C.c_void_p), int(w.size)))
         self.has_value = True
+
+    def set_weights(self, npz_path=None, value_npz=None, weights=None, value_weights=None, stream=None):
+        """ll_hl_policy_set_weights: a new model (and, with a value branch attached, a new branch) for a policy in use, uploaded in the order
+        of `stream` (None: the default stream); no recurrent state is touched."""
+        w = pack_weights(self.KIND, npz_path) if weights is None else np.ascontiguousarray(weights, dtype=np.float32)
+        v = None
+        if value_npz is not None or value_weights is not None:
+            v = pack_value_weights(self.KIND, value_npz) if value_weights is None else np.ascontiguousarray(value_weights, dtype=np.float32)
+        self._chk(self.lib.ll_hl_policy_set_weights(self.h, w.ctypes.data_as(C.c_void_p), int(w.size), v.ctypes.data_as(C.c_void_p) if v is not None else None,
+                                                    int(v.size) if v is not None else 0, _vp(stream)))
 
     def _chk(self, rc):
         if rc != 0:
