@@ -19,6 +19,7 @@
 #include "sepmc_engine.hpp"
 #include "pmc_engine.hpp"
 #include "pmc_step.hpp"
+#include "launch_plan.hpp"
 
 #define HIPCHK(call)                                                                                   \
   do {                                                                                                 \
@@ -228,7 +229,7 @@ __global__ __launch_bounds__(PMC_WAVE, OCC) void pmc_step_kernel(StepParams P) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
   const int env0 = blockIdx.x * PMC_ENVS_PER_WAVE + (threadIdx.x >> 4);      // one env = one 16-lane DPP row
   typedef WithParamsReload<typename std::conditional<OCC == 1, GpuLanesPmc1, GpuLanes>::type, LL_RELOAD_PMC> Lanes0;
-  typedef typename std::conditional<(OCC == 2 && CONE && LL_CONE_LDS), WithConeInLds<Lanes0>, Lanes0>::type Lanes;     // (launched with the row scratch allocated: launch_step)
+  typedef typename std::conditional<(OCC == 2 && CONE && LL_CONE_LDS), WithConeInLds<Lanes0>, Lanes0>::type Lanes;     // (launched with the row scratch allocated: launch_plan.hpp)
   Lanes ln(lds);
   if constexpr (OCC == 1) ln.stage_consts(P.legc, LC_COUNT, P.candc, CAND_TABLE_WORDS, P.basec);   // all 64 lanes copy, also those without an env
   else ln.stage_consts(P.legc, LC_COUNT, P.candc, CAND_TABLE_WORDS);
@@ -432,7 +433,7 @@ struct HipBackend {
   int device;
   hipStream_t own = nullptr, stream = nullptr;
   bool timing = false;
-  int simds = 1024;
+  LaunchCaps caps;                                       // what launch_plan.hpp plans the step launches by
   std::vector<std::pair<hipEvent_t, hipEvent_t>> evs;
   std::vector<int> ev_steps;                             // control steps of each timed launch (ll_step_random_n: more than one)
   size_t ev_used = 0;
@@ -447,33 +448,7 @@ struct HipBackend {
     HIPCHK(hipStreamCreateWithFlags(&own, hipStreamNonBlocking));
     hipDeviceProp_t prop;
     HIPCHK(hipGetDeviceProperties(&prop, dev));
-    simds = prop.multiProcessorCount * 4;             // four SIMDs per compute unit
-    simds_hw = simds;
-    // LL_SHARE_SIMDS=1: always launch the 256-register builds, also when the grid would fit one 512-register wavefront per SIMD.  A
-    // wavefront of the one-wave-per-SIMD builds owns its SIMD's whole register file, so any other kernel that is resident at the same
-    // time -- RCCL's gather on the learner rank -- DISPLACES step-kernel waves instead of sharing SIMDs with them, and the step launch
-    // ends later by the full residency of that kernel (measured with an RCCL stand-in: profiles/r03_simd_sharing.txt).
-    const char* sh = getenv("LL_SHARE_SIMDS");
-    if (sh && sh[0] == '1') simds = 0;
-    // LL_DETERMINISTIC=1: multi-step calls run as single launches.  A multi-step launch equals k single launches bit for bit only while every one of its waves is on the chip
-    // (ll_get_table_sync == 0); on a device it shares with other kernels -- a collective, other ranks -- a re-seed may have to take the newest table version there is, and which clip it
-    // draws then hangs on timing.  Single launches never do.
-    // LL_SEPMC_ONE_WAVE (default 1): which chase-tag build runs batches beyond one wave per SIMD.  1: the one-wave-per-SIMD build at EVERY size -- a grid of 16 x the chip's SIMDs runs as
-    // waves that follow each other on a SIMD without waiting for a step's slowest wave, and none of them spills (the 256-register chase-tag build carries 868 B of scratch per lane):
-    // 32768 arenas 5.18 -> 4.37 ms per step, 8192 arenas 1.45 -> 1.16, 4096 arenas 0.80 -> 0.61 (profiles/r06_sepmc_one_wave_ab.txt).  0: the 256-register build, two waves per SIMD
-    // (rounds 2 - 5; still what LL_SHARE_SIMDS=1 selects).  PMC and EPMC keep their 256-register builds for larger batches: those do not spill and win there.
-    const char* ow = getenv("LL_SEPMC_ONE_WAVE");
-    sepmc_simds = (simds != 0 && (ow ? ow[0] == '1' : LL_SEPMC_ONE_WAVE_DEFAULT)) ? 0x7fffffff : simds;
-    const char* ow2 = getenv("LL_EPMC_ONE_WAVE");                    // the same choice for the PlayGround env (default 0: its 256-register build does not spill and wins at larger batches)
-    epmc_simds = (simds != 0 && ow2 && ow2[0] == '1') ? 0x7fffffff : simds;
-    const char* det = getenv("LL_DETERMINISTIC");
-    deterministic = det && det[0] == '1';
-    // LL_SPLIT_RAYS (EPMC / SEPMC): 0 = the step kernel casts the 778 rays of a row itself (rounds 1 - 5); 1 = single-step launches leave them to epmc_percept_kernel behind the step
-    // kernel; 2 = multi-step calls too run as single steps, each followed by the ray kernel.  Defaults by the A/B on one box (profiles/r06_split_rays_ab.txt): EPMC 2 (hurdles: single steps
-    // 0.2983 -> 0.2905 ms, 32-step calls 0.2894 -> 0.2898; cube stairs 0.3163 -> 0.2937), SEPMC 1 (single steps 0.3341 -> 0.3308; 32-step calls would lose 4 %: 0.3153 -> 0.3286)
-    const char* sr = getenv("LL_SPLIT_RAYS");
-    split_rays_epmc = sr ? atoi(sr) : 2;
-    split_rays_sepmc = sr ? atoi(sr) : 1;
+    caps = launch_caps_from_env(prop.multiProcessorCount * 4, LL_SEPMC_ONE_WAVE_DEFAULT);             // four SIMDs per compute unit
     stream = own;
   }
   ~HipBackend() {
@@ -482,20 +457,6 @@ struct HipBackend {
     if (own) (void)hipStreamDestroy(own);
   }
   void use() { HIPCHK(hipSetDevice(device)); }
-  int simds_hw = 1024;
-  int split_rays_epmc = 2, split_rays_sepmc = 1;
-  int sepmc_simds = 1024, epmc_simds = 1024;
-  // can every workgroup of a step launch be on the chip at once?  (one 512-register wave per SIMD while the grid fits, two 256-register waves otherwise:
-  // launch_step.)  A multi-step launch needs it -- its waves wait for each other's finished episodes (PmcEngine::step)
-  bool deterministic = false;
-  bool co_resident(const StepParams& P) const {
-    const int blocks = (P.n_envs + PMC_ENVS_PER_WAVE - 1) / PMC_ENVS_PER_WAVE;
-    if (deterministic) return false;
-    // the XROWS builds run multi-step calls in one launch only within one wave per SIMD: beyond it they run as single launches (the 256-register
-    // multi-step XROWS build once returned near-3e38 entries for one env of 4352 where single launches were finite; it is not built)
-    if (pmc_launch_xrows(P, LL_ENGINE_PMC) && blocks > simds) return false;
-    return blocks <= simds || blocks <= 2 * simds_hw;
-  }
   void set_stream(void* s) { stream = s ? (hipStream_t)s : own; }
   void* stream_handle() { return (void*)stream; }
   void* alloc(size_t bytes) {
@@ -537,125 +498,78 @@ struct HipBackend {
     HIPCHK(hipEventRecord(ev->first, stream));
     return ev;
   }
-  // the rays of the step's observation by the kernel of their own?  Not when the caller plays rayTestBatch (scripted rays) -- and a multi-step call only under LL_SPLIT_RAYS=2, as single steps
-  static bool rays_split(const StepParams& P, const EpmcParams& E, int mode) { return !E.scr_ray_hit && (P.n_steps == 1 ? mode >= 1 : mode >= 2); }
   void launch_percept(const StepParams& P, const EpmcParams& E) {
     hipLaunchKernelGGL(epmc_percept_kernel, dim3(P.n_envs), dim3(PERCEPT_THREADS), 0, stream, P, E);
   }
-  void launch_epmc_step(const StepParams& P, const EpmcParams& E_in) {
-    use();
-    const int blocks = (P.n_envs + PMC_ENVS_PER_WAVE - 1) / PMC_ENVS_PER_WAVE;
-    std::pair<hipEvent_t, hipEvent_t>* ev = timing_begin(P.n_steps);
-    const bool cone = P.friction_mode == 2, split = rays_split(P, E_in, split_rays_epmc);
-    EpmcParams E = E_in;
-    E.split_rays = split ? 1 : 0;
-#define LL_GO(KERNEL, PARAMS) hipLaunchKernelGGL(KERNEL, dim3(blocks), dim3(PMC_WAVE), lds_bytes_epmc(), stream, PARAMS, E)
-    if (pmc_launch_xrows(P, LL_ENGINE_EPMC)) {          // the extended contact rows (round 6): the cone builds with XROWS, every step a launch of its own (EpmcEngine refused the pyramid)
-      StepParams Q = P;
-      Q.n_steps = 1;
-      for (int sl = 0; sl < P.n_steps; sl++, Q.step_count++) {
-        if (blocks <= epmc_simds) LL_GO((epmc_step_kernel<1, false, true, true>), Q); else LL_GO((epmc_step_kernel<2, false, true, true>), Q);
-        if (split) launch_percept(Q, E);
-      }
-    } else
-    if (P.n_steps == 1) {
-      if (blocks <= epmc_simds) { if (cone) LL_GO((epmc_step_kernel<1, false, true>), P); else LL_GO((epmc_step_kernel<1>), P); }
-      else                 { if (cone) LL_GO((epmc_step_kernel<2, false, true>), P); else LL_GO((epmc_step_kernel<2>), P); }
-      if (split) launch_percept(P, E);
-    } else if (blocks <= epmc_simds && !split) {
-      if (cone) LL_GO((epmc_step_kernel<1, true, true>), P); else LL_GO((epmc_step_kernel<1, true>), P);
-    } else {
-      StepParams Q = P;                                  // larger batches, and every batch with the rays split off: the steps of the call as single launches (see epmc_step_kernel)
-      Q.n_steps = 1;
-      for (int sl = 0; sl < P.n_steps; sl++, Q.step_count++) {
-        if (blocks <= epmc_simds) { if (cone) LL_GO((epmc_step_kernel<1, false, true>), Q); else LL_GO((epmc_step_kernel<1>), Q); }
-        else                 { if (cone) LL_GO((epmc_step_kernel<2, false, true>), Q); else LL_GO((epmc_step_kernel<2>), Q); }
-        if (split) launch_percept(Q, E);
-      }
+  // The builds that ship, by StepBuild::index(): what is not listed is not instantiated, and a plan that names it is refused, never run as something else.
+  template <class... Params> struct KernelTable {
+    typedef void (*Kernel)(StepParams, Params...);
+    Kernel at[StepBuild::kCount] = {};
+    KernelTable(std::initializer_list<std::pair<StepBuild, Kernel>> builds) { for (const auto& e : builds) at[e.first.index()] = e.second; }
+    Kernel operator[](const StepBuild& b) const {
+      if (at[b.index()]) return at[b.index()];
+      throw PmcError(LL_ESTATE, "the launch plan names a step-kernel build that is not compiled: (occ, obst, multi, cone, xrows) = (" + std::to_string(b.occ) + ", " + std::to_string(b.obst) + ", " + std::to_string(b.multi) + ", " + std::to_string(b.cone) + ", " + std::to_string(b.xrows) + ")");
     }
-#undef LL_GO
+  };
+  // EPMC and SEPMC ship the same eight: the XROWS builds and single steps at either occupancy, multi-step launches at one wave per SIMD without XROWS (see epmc_step_kernel)
+#define LL_ARENA(KERNEL, OCC, MULTI, CONE, XROWS) {{OCC, false, MULTI, CONE, XROWS}, KERNEL<OCC, MULTI, CONE, XROWS>}
+#define LL_ARENA_BUILDS(KERNEL)                                                                                                                                           \
+  {LL_ARENA(KERNEL, 1, false, true, true),  LL_ARENA(KERNEL, 2, false, true, true),   LL_ARENA(KERNEL, 1, false, true, false), LL_ARENA(KERNEL, 1, false, false, false), \
+   LL_ARENA(KERNEL, 2, false, true, false), LL_ARENA(KERNEL, 2, false, false, false), LL_ARENA(KERNEL, 1, true, true, false),  LL_ARENA(KERNEL, 1, true, false, false)}
+  static inline const KernelTable<EpmcParams> epmc_kernels LL_ARENA_BUILDS(epmc_step_kernel);
+  static inline const KernelTable<SepmcParams> sepmc_kernels LL_ARENA_BUILDS(sepmc_step_kernel);
+#undef LL_ARENA_BUILDS
+#undef LL_ARENA
+#define LL_PMC(OCC, OBST, MULTI, CONE, XROWS) {{OCC, OBST, MULTI, CONE, XROWS}, pmc_step_kernel<OCC, OBST, MULTI, CONE, XROWS>}
+  static inline const KernelTable<> pmc_kernels{
+      LL_PMC(1, false, true, true, true),  LL_PMC(1, false, false, true, true),  LL_PMC(2, false, false, true, true),      // XROWS: flat ground, the cone, multi-step within one wave per SIMD only
+      LL_PMC(1, true, true, true, false),  LL_PMC(1, true, false, true, false),  LL_PMC(2, true, true, true, false),  LL_PMC(2, true, false, true, false),
+      LL_PMC(1, true, true, false, false), LL_PMC(1, true, false, false, false), LL_PMC(2, true, true, false, false), LL_PMC(2, true, false, false, false),
+      LL_PMC(1, false, true, true, false), LL_PMC(1, false, false, true, false), LL_PMC(2, false, true, true, false), LL_PMC(2, false, false, true, false),
+      LL_PMC(1, false, true, false, false), LL_PMC(1, false, false, false, false), LL_PMC(2, false, true, false, false), LL_PMC(2, false, false, false, false)};
+#undef LL_PMC
+  StepPlan plan(int engine, const StepParams& P, bool scripted_rays = false) const { return plan_step(engine, P, scripted_rays, caps); }
+  static EpmcParams& rays_of(EpmcParams& E) { return E; } static EpmcParams& rays_of(SepmcParams& S) { return S.e; }
+  // One EPMC / SEPMC step call as its plan has it: one launch, or every step a launch of its own; ONE timing event pair around the whole call either way
+  template <class Params> void launch_arena_step(int engine, const KernelTable<Params>& kernels, const StepParams& P, const Params& X_in) {
+    use();
+    Params X = X_in;
+    EpmcParams& E = rays_of(X);
+    const StepPlan pl = plan(engine, P, E.scr_ray_hit != nullptr);
+    const auto kernel = kernels[pl.build];
+    std::pair<hipEvent_t, hipEvent_t>* ev = timing_begin(P.n_steps);
+    E.split_rays = pl.percept ? 1 : 0;
+    StepParams Q = P;
+    Q.n_steps = pl.steps_per_launch;
+    for (int done = 0; done < P.n_steps; done += Q.n_steps, Q.step_count += (uint64_t)Q.n_steps) {
+      hipLaunchKernelGGL(kernel, dim3(pl.blocks), dim3(PMC_WAVE), lds_bytes_epmc(), stream, Q, X);
+      if (pl.percept) launch_percept(Q, E);
+    }
     HIPCHK(hipGetLastError());
     if (ev) HIPCHK(hipEventRecord(ev->second, stream));
   }
+  void launch_epmc_step(const StepParams& P, const EpmcParams& E) { launch_arena_step(LL_ENGINE_EPMC, epmc_kernels, P, E); }
   void launch_epmc_reset(const StepParams& P, const EpmcParams& E, const int32_t* ids, int n, const float* draws, const float* prev_orn) {
     use();
     const int blocks = (n + PMC_ENVS_PER_WAVE - 1) / PMC_ENVS_PER_WAVE;
     hipLaunchKernelGGL(epmc_reset_kernel, dim3(blocks), dim3(PMC_WAVE), lds_bytes_epmc(), stream, P, E, ids, n, draws, prev_orn);
     HIPCHK(hipGetLastError());
   }
-  void launch_sepmc_step(const StepParams& P, const SepmcParams& S_in) {
-    use();
-    const int blocks = (P.n_envs + PMC_ENVS_PER_WAVE - 1) / PMC_ENVS_PER_WAVE;
-    std::pair<hipEvent_t, hipEvent_t>* ev = timing_begin(P.n_steps);
-    // (beyond one wave per SIMD a multi-step call is better off as single steps with the rays split off: 32768 arenas 4.52 -> 4.37 ms per step, profiles/r06_sepmc_one_wave_ab.txt)
-    const bool cone = P.friction_mode == 2, split = rays_split(P, S_in.e, (split_rays_sepmc == 1 && blocks > simds_hw) ? 2 : split_rays_sepmc);
-    SepmcParams S = S_in;
-    S.e.split_rays = split ? 1 : 0;
-#define LL_GO(KERNEL, PARAMS) hipLaunchKernelGGL(KERNEL, dim3(blocks), dim3(PMC_WAVE), lds_bytes_epmc(), stream, PARAMS, S)
-    if (pmc_launch_xrows(P, LL_ENGINE_SEPMC)) {         // the extended contact rows (round 6): see launch_epmc_step
-      StepParams Q = P;
-      Q.n_steps = 1;
-      for (int sl = 0; sl < P.n_steps; sl++, Q.step_count++) {
-        if (blocks <= sepmc_simds) LL_GO((sepmc_step_kernel<1, false, true, true>), Q); else LL_GO((sepmc_step_kernel<2, false, true, true>), Q);
-        if (split) launch_percept(Q, S.e);
-      }
-    } else
-    if (P.n_steps == 1) {
-      if (blocks <= sepmc_simds) { if (cone) LL_GO((sepmc_step_kernel<1, false, true>), P); else LL_GO((sepmc_step_kernel<1>), P); }
-      else                 { if (cone) LL_GO((sepmc_step_kernel<2, false, true>), P); else LL_GO((sepmc_step_kernel<2>), P); }
-      if (split) launch_percept(P, S.e);
-    } else if (blocks <= sepmc_simds && !split) {
-      if (cone) LL_GO((sepmc_step_kernel<1, true, true>), P); else LL_GO((sepmc_step_kernel<1, true>), P);
-    } else {
-      StepParams Q = P;                                  // larger batches, and every batch with the rays split off: single launches (see epmc_step_kernel)
-      Q.n_steps = 1;
-      for (int sl = 0; sl < P.n_steps; sl++, Q.step_count++) {
-        if (blocks <= sepmc_simds) { if (cone) LL_GO((sepmc_step_kernel<1, false, true>), Q); else LL_GO((sepmc_step_kernel<1>), Q); }
-        else                 { if (cone) LL_GO((sepmc_step_kernel<2, false, true>), Q); else LL_GO((sepmc_step_kernel<2>), Q); }
-        if (split) launch_percept(Q, S.e);
-      }
-    }
-#undef LL_GO
-    HIPCHK(hipGetLastError());
-    if (ev) HIPCHK(hipEventRecord(ev->second, stream));
-  }
+  void launch_sepmc_step(const StepParams& P, const SepmcParams& S) { launch_arena_step(LL_ENGINE_SEPMC, sepmc_kernels, P, S); }
   void launch_sepmc_reset(const StepParams& P, const SepmcParams& S, const int32_t* ids, int n, const float* draws, const float* prev_orn) {
     use();
     const int blocks = (n + PMC_ENVS_PER_WAVE - 1) / PMC_ENVS_PER_WAVE;
     hipLaunchKernelGGL(sepmc_reset_kernel, dim3(blocks), dim3(PMC_WAVE), lds_bytes_epmc(), stream, P, S, ids, n, draws, prev_orn);
     HIPCHK(hipGetLastError());
   }
+  // One planned PMC launch.  PmcEngine::step has cut the call by the same plan: a launch of more steps than the plan carries is refused, never run as something else
   void launch_step(const StepParams& P) {
     use();
-    const int blocks = (P.n_envs + PMC_ENVS_PER_WAVE - 1) / PMC_ENVS_PER_WAVE;
+    const StepPlan pl = plan(LL_ENGINE_PMC, P);
+    if (P.n_steps > pl.steps_per_launch) throw PmcError(LL_ESTATE, "a launch of " + std::to_string(P.n_steps) + " control steps where the launch plan carries at most " + std::to_string(pl.steps_per_launch));
+    const auto kernel = pmc_kernels[pl.build];
     std::pair<hipEvent_t, hipEvent_t>* ev = timing_begin(P.n_steps);
-    const bool one = blocks <= simds, multi = P.n_steps > 1;
-    if (pmc_launch_xrows(P, LL_ENGINE_PMC)) {           // the extended contact rows (round 6): flat-ground cone builds with XROWS (PmcEngine refused the pyramid and the obstacle)
-      if (one) { if (multi) hipLaunchKernelGGL((pmc_step_kernel<1, false, true, true, true>), dim3(blocks), dim3(PMC_WAVE), lds_bytes(), stream, P);
-                 else       hipLaunchKernelGGL((pmc_step_kernel<1, false, false, true, true>), dim3(blocks), dim3(PMC_WAVE), lds_bytes(), stream, P); }
-      else       hipLaunchKernelGGL((pmc_step_kernel<2, false, false, true, true>), dim3(blocks), dim3(PMC_WAVE), lds_bytes_epmc(), stream, P);    // (single steps only: co_resident)
-    } else
-    if (P.set_obstacle && P.friction_mode == 2) {
-      if (one) { if (multi) hipLaunchKernelGGL((pmc_step_kernel<1, true, true, true>), dim3(blocks), dim3(PMC_WAVE), lds_bytes_epmc(), stream, P);
-                 else       hipLaunchKernelGGL((pmc_step_kernel<1, true, false, true>), dim3(blocks), dim3(PMC_WAVE), lds_bytes_epmc(), stream, P); }
-      else     { if (multi) hipLaunchKernelGGL((pmc_step_kernel<2, true, true, true>), dim3(blocks), dim3(PMC_WAVE), lds_bytes_epmc(), stream, P);
-                 else       hipLaunchKernelGGL((pmc_step_kernel<2, true, false, true>), dim3(blocks), dim3(PMC_WAVE), lds_bytes_epmc(), stream, P); }
-    } else if (P.set_obstacle) {
-      if (one) { if (multi) hipLaunchKernelGGL((pmc_step_kernel<1, true, true>), dim3(blocks), dim3(PMC_WAVE), lds_bytes_epmc(), stream, P);
-                 else       hipLaunchKernelGGL((pmc_step_kernel<1, true, false>), dim3(blocks), dim3(PMC_WAVE), lds_bytes_epmc(), stream, P); }
-      else     { if (multi) hipLaunchKernelGGL((pmc_step_kernel<2, true, true>), dim3(blocks), dim3(PMC_WAVE), lds_bytes_epmc(), stream, P);
-                 else       hipLaunchKernelGGL((pmc_step_kernel<2, true, false>), dim3(blocks), dim3(PMC_WAVE), lds_bytes_epmc(), stream, P); }
-    } else if (P.friction_mode == 2) {
-      if (one) { if (multi) hipLaunchKernelGGL((pmc_step_kernel<1, false, true, true>), dim3(blocks), dim3(PMC_WAVE), lds_bytes(), stream, P);
-                 else       hipLaunchKernelGGL((pmc_step_kernel<1, false, false, true>), dim3(blocks), dim3(PMC_WAVE), lds_bytes(), stream, P); }
-      else     { if (multi) hipLaunchKernelGGL((pmc_step_kernel<2, false, true, true>), dim3(blocks), dim3(PMC_WAVE), lds_bytes_epmc(), stream, P);      // (row scratch: WithConeInLds)
-                 else       hipLaunchKernelGGL((pmc_step_kernel<2, false, false, true>), dim3(blocks), dim3(PMC_WAVE), lds_bytes_epmc(), stream, P); }
-    } else {
-      if (one) { if (multi) hipLaunchKernelGGL((pmc_step_kernel<1, false, true>), dim3(blocks), dim3(PMC_WAVE), lds_bytes(), stream, P);
-                 else       hipLaunchKernelGGL((pmc_step_kernel<1, false, false>), dim3(blocks), dim3(PMC_WAVE), lds_bytes(), stream, P); }
-      else     { if (multi) hipLaunchKernelGGL((pmc_step_kernel<2, false, true>), dim3(blocks), dim3(PMC_WAVE), lds_bytes(), stream, P);
-                 else       hipLaunchKernelGGL((pmc_step_kernel<2, false, false>), dim3(blocks), dim3(PMC_WAVE), lds_bytes(), stream, P); }
-    }
+    hipLaunchKernelGGL(kernel, dim3(pl.blocks), dim3(PMC_WAVE), pl.row_scratch ? lds_bytes_epmc() : lds_bytes(), stream, P);
     HIPCHK(hipGetLastError());
     if (ev) HIPCHK(hipEventRecord(ev->second, stream));
   }

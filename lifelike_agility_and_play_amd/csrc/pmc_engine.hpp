@@ -8,6 +8,7 @@
 
 #include "pmc_params.hpp"
 #include "pmc_tables.hpp"
+#include "launch_plan.hpp"
 
 struct PmcError : public std::runtime_error {
   int code;
@@ -196,8 +197,8 @@ struct PmcEngine {
     need(true, true);
     need_launchable(LL_ENGINE_PMC);
     // A launch runs at most LL_MAX_STEPS_PER_LAUNCH control steps (the per-step slots of the sampling table), and a multi-step launch whose grid
-    // the chip cannot hold at once runs as single launches: its waves could not wait for each other's finished episodes (bk.co_resident)
-    const int per = (n_steps > 1 && !bk.co_resident(P)) ? 1 : LL_MAX_STEPS_PER_LAUNCH;
+    // the chip cannot hold at once runs as single launches: its waves could not wait for each other's finished episodes (launch_plan.hpp)
+    const int per = steps_per_launch(bk, P, 0);
     for (int done = 0; done < n_steps;) {
       const int k = n_steps - done < per ? n_steps - done : per;
       StepParams Q = P;
@@ -213,6 +214,8 @@ struct PmcEngine {
       done += k;
     }
   }
+  template <class B> static auto steps_per_launch(const B& b, const StepParams& P, int) -> decltype(b.plan(0, P).steps_per_launch) { return b.plan(LL_ENGINE_PMC, P).steps_per_launch; }
+  template <class B> static int steps_per_launch(const B&, const StepParams&, long) { return LL_MAX_STEPS_PER_LAUNCH; }      // a backend written before launch_plan.hpp (no plan()): whole launches
   uint32_t launch_serial = 0;
   void step_random(float sigma) {
     if (!(sigma > 0.0f)) throw PmcError(LL_EINVAL, "sigma must be positive");

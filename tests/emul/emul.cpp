@@ -3,6 +3,7 @@
 // library so one Python harness drives both.  Purpose: debug the kernel's logic against the oracle on a machine
 // without a GPU.  Built only by the tests into tests/emul/_build/; the product never loads it.
 #include "lanes_host.hpp"
+#include "plan_point.hpp"
 
 #include <stdlib.h>
 #include <string.h>
@@ -26,14 +27,28 @@ struct HostBackend {
   void h2d(void* d, const void* h, size_t bytes) { memcpy(d, h, bytes); }
   void d2h(void* h, const void* d, size_t bytes) { memcpy(h, d, bytes); }
   void sync() {}
+  // The host's own caps for launch_plan.hpp: one wave per SIMD and co-resident at every size; LL_SPLIT_RAYS read per call (a test can run both ways in one process): >= 1 splits, whatever n_steps
+  StepPlan plan(int engine, const StepParams& P, bool scripted_rays = false) const {
+    const char* v = getenv("LL_SPLIT_RAYS"); const int big = 0x7fffffff, mode = (v && atoi(v) >= 1) ? 2 : 0;
+    return plan_step(engine, P, scripted_rays, LaunchCaps{big, big, big, big, false, mode, mode});
+  }
+  // The host instantiation of a planned build, as HipBackend looks its kernel up: f(obst, cone, xrows) with the three as compile-time constants, for the builds the kernel source has
+  template <class FN> static void with_build(const StepBuild& b, FN f) {
+    typedef std::true_type Y; typedef std::false_type N;
+    switch (b.obst | b.cone << 1 | b.xrows << 2) {
+      case 0: return f(N(), N(), N());
+      case 1: return f(Y(), N(), N());
+      case 2: return f(N(), Y(), N());
+      case 3: return f(Y(), Y(), N());
+      case 6: return f(N(), Y(), Y());      // the extended contact rows: cone builds without the obstacle
+    }
+    throw PmcError(LL_ESTATE, "the launch plan names a build the host has no instantiation of: (obst, cone, xrows) = (" + std::to_string(b.obst) + ", " + std::to_string(b.cone) + ", " + std::to_string(b.xrows) + ")");
+  }
   void launch_step(const StepParams& P) {
     HostLanes ln(P.candc);
+    const StepBuild b = plan(LL_ENGINE_PMC, P).build;
     for (int sl = 0; sl < P.n_steps; sl++) {               // ll_step_random_n: step-major, the table folded after every step into that step's version
-      if (P.action_sigma > 0.0f) {
-        StepParams Q = P;
-        Q.step_count = P.step_count + (uint64_t)sl;
-        launch_actions(Q, P.actions_out, P.action_sigma);
-      }
+      draw_step_actions(P, sl);
       for (int env = 0; env < P.n_envs; env++) {
         fN act[3];
         for (int j = 0; j < 3; j++) act[j] = ln.ldl(P.actions, (long)env * 12 + j, 3);
@@ -47,16 +62,11 @@ struct HostBackend {
           if (P.set_obstacle) Pmc<HostLanesPipe>::step_env<true, true>(lq, P, env, act, sl);
           else Pmc<HostLanesPipe>::step_env<false, true>(lq, P, env, act, sl);
         }
-        else if (pmc_launch_xrows(P, LL_ENGINE_PMC)) K::step_env<false, true, true>(ln, P, env, act, sl);   // the extended contact rows (llenv.hip launch_step): the XROWS build
-        else if (P.set_obstacle && P.friction_mode == 2) K::step_env<true, true>(ln, P, env, act, sl);
-        else if (P.set_obstacle) K::step_env<true>(ln, P, env, act, sl);
-        else if (P.friction_mode == 2) K::step_env<false, true>(ln, P, env, act, sl);
-        else K::step_env<false>(ln, P, env, act, sl);
+        else with_build(b, [&](auto obst, auto cone, auto xrows) { K::step_env<obst(), cone(), xrows()>(ln, P, env, act, sl); });
       }
       pmc_finalize_table(P, sl, sl == P.n_steps - 1);
     }
   }
-  bool co_resident(const StepParams&) const { return true; }
   void launch_reset(const StepParams& P, const int32_t* ids, int n, const int32_t* clip, const double* t0) {
     HostLanes ln(P.candc);
     for (int i = 0; i < n; i++) {
@@ -107,12 +117,11 @@ struct HostBackend {
     Q.step_count = P.step_count + (uint64_t)sl;
     launch_actions(Q, P.actions_out, P.action_sigma);
   }
-  // LL_SPLIT_RAYS (as llenv.hip HipBackend; read per call here so that a test can run both ways in one process): the 778 rays of a row after the step, by Epmc::percept_row_host
-  static bool rays_split(const EpmcParams& E) { const char* v = getenv("LL_SPLIT_RAYS"); return v && atoi(v) >= 1 && !E.scr_ray_hit; }
   void launch_epmc_step(const StepParams& P, const EpmcParams& E_in) {
     HostLanes ln(P.candc);
+    const StepPlan pl = plan(LL_ENGINE_EPMC, P, E_in.scr_ray_hit != nullptr);
     EpmcParams E = E_in;
-    E.split_rays = rays_split(E_in) ? 1 : 0;
+    E.split_rays = pl.percept ? 1 : 0;         // the 778 rays of a row after the step, by Epmc::percept_row_host
     for (int sl = 0; sl < P.n_steps; sl++) {
       draw_step_actions(P, sl);
       for (int env = 0; env < P.n_envs; env++) {
@@ -120,8 +129,7 @@ struct HostBackend {
         for (int j = 0; j < 3; j++) act[j] = ln.ldl(P.actions, (long)env * 12 + j, 3);
         const bool park = getenv("LL_EMUL_PARK") != nullptr, cone = P.friction_mode == 2;      // park: the larger-batch GPU build's variant (tests)
         if (park) { if (cone) { HostLanesLds lq(P.candc); Epmc<HostLanesLds>::step_env<true, true>(lq, P, E, env, act); } else Epmc<HostLanes>::step_env<true>(ln, P, E, env, act); }
-        else if (pmc_launch_xrows(P, LL_ENGINE_EPMC)) Epmc<HostLanes>::step_env<false, true, true>(ln, P, E, env, act);
-        else      { if (cone) Epmc<HostLanes>::step_env<false, true>(ln, P, E, env, act); else Epmc<HostLanes>::step_env(ln, P, E, env, act); }
+        else with_build(pl.build, [&](auto, auto cone, auto xrows) { Epmc<HostLanes>::step_env<false, cone(), xrows()>(ln, P, E, env, act); });
         if (E.split_rays) Epmc<HostLanes>::percept_row_host(P, E, env);
       }
     }
@@ -147,8 +155,9 @@ struct HostBackend {
     }
   }
   void launch_sepmc_step(const StepParams& P, const SepmcParams& S_in) {
+    const StepPlan pl = plan(LL_ENGINE_SEPMC, P, S_in.e.scr_ray_hit != nullptr);
     SepmcParams S = S_in;
-    S.e.split_rays = rays_split(S_in.e) ? 1 : 0;
+    S.e.split_rays = pl.percept ? 1 : 0;
     for (int sl = 0; sl < P.n_steps; sl++) {
       draw_step_actions(P, sl);
       const bool park = getenv("LL_EMUL_PARK") != nullptr, cone = P.friction_mode == 2;
@@ -163,9 +172,7 @@ struct HostBackend {
           fN act[3];
           for (int j = 0; j < 3; j++) act[j] = ln.ldl(P.actions, (long)row * 12 + j, 3);
           if (park) Sepmc<HostLanes>::step_env<true>(ln, P, S, row, act);
-          else if (pmc_launch_xrows(P, LL_ENGINE_SEPMC)) Sepmc<HostLanes>::step_env<false, true, true>(ln, P, S, row, act);
-          else if (cone) Sepmc<HostLanes>::step_env<false, true>(ln, P, S, row, act);
-          else Sepmc<HostLanes>::step_env(ln, P, S, row, act);
+          else with_build(pl.build, [&](auto, auto cone, auto xrows) { Sepmc<HostLanes>::step_env<false, cone(), xrows()>(ln, P, S, row, act); });
         });
       if (S.e.split_rays)
         for (int row = 0; row < P.n_envs; row++) Epmc<HostLanes>::percept_row_host(P, S.e, row);
@@ -209,6 +216,21 @@ int emu_substep(ll_engine* h, float* state37, const float* tgt12) {
   state37[10] = bs.w.x; state37[11] = bs.w.y; state37[12] = bs.w.z;
   for (int j = 0; j < 3; j++)
     for (int l = 0; l < 4; l++) { state37[13 + 3 * l + j] = q[j].v[4 * l]; state37[25 + 3 * l + j] = qd[j].v[4 * l]; }
+  return 0;
+}
+// the launch plan of one step call under explicit caps (plan_point.hpp), and the caps the product reads from the environment for a device of simds_hw SIMDs
+int emu_step_plan(int engine, const double* spec6, int n_envs, int n_steps, int scripted_rays, const int* caps7, int* plan8) {
+  plan_point(engine, spec6, n_envs, n_steps, scripted_rays, caps7, plan8);
+  return 0;
+}
+int emu_host_build(int obst, int cone, int xrows) {      // has the host an instantiation of this build?  0, or the code of HostBackend's refusal
+  try { HostBackend::with_build(StepBuild{1, obst != 0, false, cone != 0, xrows != 0}, [](auto, auto, auto) {}); } catch (const PmcError& e) { return e.code; }
+  return 0;
+}
+int emu_launch_caps(int simds_hw, int sepmc_one_wave_default, int* caps7) {
+  const LaunchCaps c = launch_caps_from_env(simds_hw, sepmc_one_wave_default != 0);
+  const int out[7] = {c.simds_hw, c.simds, c.epmc_simds, c.sepmc_simds, c.deterministic, c.split_rays_epmc, c.split_rays_sepmc};
+  memcpy(caps7, out, sizeof out);
   return 0;
 }
 }

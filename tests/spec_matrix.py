@@ -94,7 +94,7 @@ def header_spec_ids(path):
     return ids, ids.pop('count')
 
 
-# ---- the step-kernel builds (llenv.hip HipBackend::launch_step / launch_epmc_step / launch_sepmc_step) --------------------------------------------------
+# ---- the step-kernel builds: an independent restatement of csrc/launch_plan.hpp, held to it by test_spec_matrix_emul.py --------------------------------------
 # A build is (kernel, OCC, OBST, MULTI, CONE, XROWS); EPMC and SEPMC have no OBST argument (False here).  OCC 1: one wave per SIMD (n <= 4096 envs on the
 # MI355X's 1024 SIMDs), OCC 2: the 256-register build of larger batches.
 
@@ -107,7 +107,7 @@ def expected_builds(engine, spec, occ, multi, split_rays=None):
     cone = int(spec.get('friction_mode', 2)) == 2
     if engine in ('pmc', 'pmc_obst'):
         obst = engine == 'pmc_obst'
-        if spec.get('self_friction', 0) > 0:                     # (beyond one wave per SIMD a multi-step call runs as single launches: HipBackend::co_resident)
+        if spec.get('self_friction', 0) > 0:                     # (beyond one wave per SIMD a multi-step call runs as single launches)
             return {('pmc_step_kernel', occ, False, multi and occ == 1, True, True)}
         return {('pmc_step_kernel', occ, obst, multi, cone, False)}
     kernel = engine + '_step_kernel'
@@ -127,19 +127,23 @@ MULTI_CHECKS = [(e, dict(friction_mode=m), (1, 2) if e in ('pmc', 'pmc_obst') el
                [('pmc', dict(self_friction=0.25), (1, 2), False)]
 
 
+def launchable_cells():
+    """(row, engine, mode, spec) of every PARITY / INERT cell: the runs the table has that launch something"""
+    for name, row in ROWS.items():
+        for engine, modes in row['engines'].items():
+            for mode, outcome in modes.items():
+                if outcome in (PARITY, INERT):
+                    yield name, engine, mode, ({**spec_of(name, row['values'][0]), 'friction_mode': mode} if name != 'friction_mode' else {'friction_mode': row['values'][0]})
+
+
 def claimed_builds():
     """every build a check of the table reaches: the single-step builds of each PARITY / INERT cell at either occupancy (the parity comparators
     step one launch at a time), and the builds of the multi-step legs (MULTI_CHECKS).  build -> [(row or 'multi', engine, mode)]"""
     out = {}
-    for name, row in ROWS.items():
-        for engine, modes in row['engines'].items():
-            for mode, outcome in modes.items():
-                if outcome not in (PARITY, INERT):
-                    continue
-                spec = {**spec_of(name, row['values'][0]), 'friction_mode': mode} if name != 'friction_mode' else {'friction_mode': row['values'][0]}
-                for occ in (1, 2):
-                    for b in expected_builds(engine, spec, occ, False):
-                        out.setdefault(b, []).append((name, engine, mode))
+    for name, engine, mode, spec in launchable_cells():
+        for occ in (1, 2):
+            for b in expected_builds(engine, spec, occ, False):
+                out.setdefault(b, []).append((name, engine, mode))
     for engine, spec, occs, split in MULTI_CHECKS:
         for occ in occs:
             for b in expected_builds(engine, spec, occ, True, split_rays=split):
