@@ -127,16 +127,24 @@ EXPORTED_SYMBOLS = sorted(_SIGS)
 _libs = {}
 
 
+def bind(lib, sigs):
+    """restype / argtypes of every entry point of `sigs` (a module's _SIGS), set once per library object; -> lib"""
+    bound = lib.__dict__.setdefault('_ll_bound', [])
+    if not any(b is sigs for b in bound):
+        for name, (res, args) in sigs.items():
+            fn = getattr(lib, name)           # AttributeError if the library lacks a declared symbol
+            fn.restype, fn.argtypes = res, args
+        bound.append(sigs)
+    return lib
+
+
 def load_library(path=None):
     path = os.path.abspath(path or DEFAULT_LIB)
     if path not in _libs:
         if not os.path.exists(path):
             raise ImportError('%s not found: build it with `python -c "import __graft_entry__ as g; g.build()"` '
                               '(hipcc --offload-arch=gfx950). There is no CPU fallback.' % path)
-        lib = C.CDLL(path)
-        for name, (res, args) in _SIGS.items():
-            fn = getattr(lib, name)           # AttributeError if the library lacks a declared symbol
-            fn.restype, fn.argtypes = res, args
+        lib = bind(C.CDLL(path), _SIGS)
         if lib.ll_abi_version() != LL_ABI_VERSION:
             raise ImportError('%s speaks ABI version %d, this binding %d: rebuild the library (__graft_entry__.build())' % (path, lib.ll_abi_version(), LL_ABI_VERSION))
         _libs[path] = lib
@@ -147,14 +155,117 @@ def _ptr(a):
     return a.ctypes.data_as(C.c_void_p) if a is not None else None
 
 
-class Engine(object):
+class NativeHandle(object):
+    """One native handle `h` of `lib`, destroyed by `lib.<_destroy>(h)`: by close() or when the object goes, once, and only in the process that
+    created it (a fork()ed child inherits the Python object, not the HIP context).  After close() `h` is None; close() is safe on an object
+    whose constructor raised, wherever it raised."""
+    _destroy = None
+
+    def _open(self, lib):
+        """the first thing a constructor does; the native create call then fills self.h (C.byref(self.h))"""
+        self.lib, self._pid, self.h = lib, os.getpid(), C.c_void_p()
+
+    def _chk(self, rc):
+        if rc != 0:
+            raise LLError(rc, self.lib.ll_last_error().decode())
+
+    def close(self):
+        h, self.h = getattr(self, 'h', None), None
+        if h and getattr(self, '_pid', None) == os.getpid():
+            getattr(self.lib, self._destroy)(h)
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:     # noqa: BLE001
+            pass
+
+
+class EngineBase(NativeHandle):
+    """What the bindings of the three engines share: the entry points that differ in their prefix (`_prefix`: 'll_', 'll_epmc_', 'll_sepmc_')
+    and in the leading shape of a per-robot array (`_rows`: (n_envs,) or (n_arenas, 2))."""
+    _prefix, _steps_key = None, 'env_steps'
+
+    def _call(self, name, *args):
+        self._chk(getattr(self.lib, self._prefix + name)(self.h, *args))
+
+    def step(self, d_actions_ptr=None):
+        """d_actions_ptr: integer device address of float32 [rows][12], or None for the engine's action buffer."""
+        self._call('step', C.c_void_p(int(d_actions_ptr)) if d_actions_ptr else None)
+
+    def step_host(self, actions):
+        a = np.ascontiguousarray(actions, dtype=np.float32).reshape(self._rows + (12,))
+        self._call('set_actions', _ptr(a))
+        self.step(None)
+
+    def fill_random_actions(self, sigma):
+        self._call('fill_random_actions', float(sigma))
+
+    def step_random_n(self, sigma, n_steps):
+        """n_steps x {fill_random_actions(sigma); step()} in ONE launch (ll_*_step_random_n)"""
+        self._call('step_random_n', float(sigma), int(n_steps))
+
+    def sync(self):
+        self._call('sync')
+
+    def set_spec(self, **kw):
+        """Deviation study (ll_*_set_spec_param): the physics-spec switches of include/llenv_model.h (the robot and its solver are the PMC
+        engine's in all three), e.g. set_spec(limit_gate=1e30, max_contacts_per_leg=2), set_spec(friction_mode=2)."""
+        for k, v in kw.items():
+            self._call('set_spec_param', SPEC_IDS[k], float(v))
+
+    def get_spec(self, key):
+        v = C.c_double()
+        self._call('get_spec_param', SPEC_IDS[key], C.byref(v))
+        return v.value
+
+    def device_ptrs(self):
+        """Device addresses of obs / reward / done / actions and the engine's stream (gather.engine_tensors, gather.use_engine_stream)."""
+        p = LLDevicePtrs()
+        self._call('device_ptrs', C.byref(p))
+        return p
+
+    def obs(self):
+        o = np.empty(self._rows + (self.obs_dim,), dtype=np.float32)
+        self._call('get_obs', _ptr(o))
+        return o
+
+    def state(self):
+        s = np.empty(self._rows + (37,), dtype=np.float32)
+        self._call('get_state', _ptr(s))
+        return s
+
+    def set_state(self, s):
+        s = np.ascontiguousarray(s, dtype=np.float32).reshape(self._rows + (37,))
+        self._call('set_state', _ptr(s))
+
+    def counters(self):
+        a, b, c = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
+        self._call('get_counters', C.byref(a), C.byref(b), C.byref(c))
+        return {self._steps_key: a.value, 'episodes': b.value, 'nonfinite': c.value}
+
+    def enable_kernel_timing(self, on=True):
+        self._call('enable_kernel_timing', 1 if on else 0)
+
+    def kernel_time_ms(self):
+        ms, n = C.c_double(), C.c_int()
+        self._call('kernel_time_ms', C.byref(ms), C.byref(n))
+        return ms.value, n.value
+
+    def kernel_time_stats(self):
+        """-> (average ms per launch, launches, control steps those launches ran)"""
+        ms, n, st = C.c_double(), C.c_int(), C.c_int64()
+        self._call('kernel_time_stats', C.byref(ms), C.byref(n), C.byref(st))
+        return ms.value, n.value, st.value
+
+
+class Engine(EngineBase):
     """One batch of environments on one GPU (ll_engine)."""
+    _prefix, _destroy = 'll_', 'll_destroy'
 
     def __init__(self, cfg, model_blob, mocap_table, lib_path=None):
-        self.lib = load_library(lib_path)
+        self._open(load_library(lib_path))
         self.cfg = cfg
-        self._pid = os.getpid()      # a handle is only ever destroyed by the process that created it (a fork()ed child inherits the Python object, not the HIP context)
-        self.h = C.c_void_p()
         blob = np.ascontiguousarray(model_blob, dtype=np.float64)
         self._chk(self.lib.ll_create(C.byref(cfg), _ptr(blob), int(blob.size), C.byref(self.h)))
         frames = np.ascontiguousarray(mocap_table.frames)
@@ -173,21 +284,9 @@ class Engine(object):
         p = self.device_ptrs()
         self.obs_dim = p.obs_dim
 
-    def _chk(self, rc):
-        if rc != 0:
-            raise LLError(rc, self.lib.ll_last_error().decode())
-
-    def close(self):
-        if self.h:
-            if getattr(self, '_pid', None) == os.getpid():
-                self.lib.ll_destroy(self.h)
-            self.h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+    @property
+    def _rows(self):
+        return (self.n_envs,)
 
     # ---- control ------------------------------------------------------------------------------------
     def reset(self, env_ids=None, clip=None, t0=None):
@@ -199,15 +298,6 @@ class Engine(object):
             if a is not None and len(a) != n:
                 raise ValueError('clip / t0 must have one entry per reset env')
         self._chk(self.lib.ll_reset(self.h, _ptr(ids), n, _ptr(cl), _ptr(tt)))
-
-    def step(self, d_actions_ptr=None):
-        """d_actions_ptr: integer device address of float32 [n_envs][12], or None for the engine's action buffer."""
-        self._chk(self.lib.ll_step(self.h, C.c_void_p(d_actions_ptr) if d_actions_ptr else None))
-
-    def step_host(self, actions):
-        a = np.ascontiguousarray(actions, dtype=np.float32).reshape(self.n_envs, 12)
-        self._chk(self.lib.ll_set_actions(self.h, _ptr(a)))
-        self.step(None)
 
     def step_scripted(self, actions, state, feet=None):
         """Parity hook (ll_step_scripted): host actions [n][12], physics result state [n][37], optional feet [n][2][4][3]."""
@@ -225,29 +315,9 @@ class Engine(object):
         self._chk(self.lib.ll_probe_pd_torque(self.h, _ptr(rows), len(rows), int(mode), _ptr(tau)))
         return tau
 
-    def set_spec(self, **kw):
-        """Deviation study (ll_set_spec_param): e.g. set_spec(limit_gate=1e30, max_contacts_per_leg=2)."""
-        for k, v in kw.items():
-            self._chk(self.lib.ll_set_spec_param(self.h, SPEC_IDS[k], float(v)))
-
-    def get_spec(self, key):
-        v = C.c_double()
-        self._chk(self.lib.ll_get_spec_param(self.h, SPEC_IDS[key], C.byref(v)))
-        return v.value
-
-    def fill_random_actions(self, sigma):
-        self._chk(self.lib.ll_fill_random_actions(self.h, float(sigma)))
-
     def step_random(self, sigma):
         """fill_random_actions(sigma) + step() as one kernel launch."""
         self._chk(self.lib.ll_step_random(self.h, float(sigma)))
-
-    def step_random_n(self, sigma, n_steps):
-        """n_steps iterations of the random-policy loop in ONE launch (ll_step_random_n)."""
-        self._chk(self.lib.ll_step_random_n(self.h, float(sigma), int(n_steps)))
-
-    def sync(self):
-        self._chk(self.lib.ll_sync(self.h))
 
     def set_stream(self, stream_handle):
         if stream_handle is not None and int(stream_handle) == 0:
@@ -281,17 +351,7 @@ class Engine(object):
     def finish_unroll(self, buffer, gamma, lam, d_bootstrap_value=None):
         self._chk(self.lib.ll_finish_unroll(self.h, int(buffer), float(gamma), float(lam), C.c_void_p(int(d_bootstrap_value)) if d_bootstrap_value else None))
 
-    def device_ptrs(self):
-        p = LLDevicePtrs()
-        self._chk(self.lib.ll_device_ptrs(self.h, C.byref(p)))
-        return p
-
     # ---- host copies ------------------------------------------------------------------------------------
-    def obs(self):
-        o = np.empty((self.n_envs, self.obs_dim), dtype=np.float32)
-        self._chk(self.lib.ll_get_obs(self.h, _ptr(o)))
-        return o
-
     def terminal_obs(self):
         o = np.empty((self.n_envs, self.obs_dim), dtype=np.float32)
         self._chk(self.lib.ll_get_terminal_obs(self.h, _ptr(o)))
@@ -303,15 +363,6 @@ class Engine(object):
         why = np.empty(self.n_envs, dtype=np.uint8)
         self._chk(self.lib.ll_get_reward_done(self.h, _ptr(r), _ptr(d), _ptr(why)))
         return r, d.astype(bool), why
-
-    def state(self):
-        s = np.empty((self.n_envs, 37), dtype=np.float32)
-        self._chk(self.lib.ll_get_state(self.h, _ptr(s)))
-        return s
-
-    def set_state(self, s):
-        s = np.ascontiguousarray(s, dtype=np.float32).reshape(self.n_envs, 37)
-        self._chk(self.lib.ll_set_state(self.h, _ptr(s)))
 
     def ref_state(self):
         s = np.empty((self.n_envs, 37), dtype=np.float32)
@@ -346,27 +397,8 @@ class Engine(object):
         self._chk(self.lib.ll_get_table_sync(self.h, C.byref(a)))
         return a.value
 
-    def counters(self):
-        a, b, c = C.c_uint64(), C.c_uint64(), C.c_uint64()
-        self._chk(self.lib.ll_get_counters(self.h, C.byref(a), C.byref(b), C.byref(c)))
-        return dict(env_steps=a.value, episodes=b.value, nonfinite=c.value)
-
     def episode_histogram(self):
         """finished episodes by length: counts[b] = episodes of 2^b .. 2^(b+1) - 1 control steps (b = 15: and longer)"""
         c = np.zeros(16, dtype=np.uint64)
         self._chk(self.lib.ll_get_episode_histogram(self.h, _ptr(c)))
         return c
-
-    def enable_kernel_timing(self, on=True):
-        self._chk(self.lib.ll_enable_kernel_timing(self.h, int(on)))
-
-    def kernel_time_ms(self):
-        ms, n = C.c_double(), C.c_int()
-        self._chk(self.lib.ll_kernel_time_ms(self.h, C.byref(ms), C.byref(n)))
-        return ms.value, n.value
-
-    def kernel_time_stats(self):
-        """-> (average ms per launch, launches, control steps those launches ran)"""
-        ms, n, st = C.c_double(), C.c_int(), C.c_int64()
-        self._chk(self.lib.ll_kernel_time_stats(self.h, C.byref(ms), C.byref(n), C.byref(st)))
-        return ms.value, n.value, st.value

@@ -3,64 +3,17 @@
 struct ll_epmc_engine {
   EPMC_ENGINE* e;
 };
+static const EpmcParams& ll_play(ll_epmc_engine* h) { return h->e->E; }
 
 extern "C" {
 
-int ll_epmc_create(const ll_epmc_config* cfg, const double* model_blob, int blob_len, const double* init_state37, ll_epmc_engine** out) {
-  LL_TRY
-  LL_CHECK(cfg && model_blob && init_state37 && out, "null argument");
-  *out = nullptr;
-  ll_epmc_engine* h = new ll_epmc_engine;
-  try {
-    h->e = new EPMC_ENGINE(*cfg, model_blob, blob_len, init_state37);
-  } catch (...) {
-    delete h;
-    throw;
-  }
-  *out = h;
-  LL_CATCH
-}
-int ll_epmc_destroy(ll_epmc_engine* h) {
-  LL_TRY
-  if (h) {
-    delete h->e;
-    delete h;
-  }
-  LL_CATCH
-}
-int ll_epmc_reset(ll_epmc_engine* h, const int32_t* env_ids, int n, const float* h_draws, const float* h_prev_orn) {
-  LL_TRY
-  LL_CHECK(h, "null engine");
-  h->e->reset(env_ids, n, h_draws, h_prev_orn);
-  LL_CATCH
-}
-int ll_epmc_step(ll_epmc_engine* h, const float* d_actions) {
-  LL_TRY
-  LL_CHECK(h, "null engine");
-  h->e->step(d_actions);
-  LL_CATCH
-}
-int ll_epmc_step_random_n(ll_epmc_engine* h, float sigma, int n_steps) {
-  LL_TRY
-  LL_CHECK(h, "null engine");
-  h->e->step_random_n(sigma, n_steps);
-  LL_CATCH
-}
-int ll_epmc_kernel_time_stats(ll_epmc_engine* h, double* avg_launch_ms, int* n_launches, int64_t* n_control_steps) {
-  LL_TRY
-  LL_CHECK(h && avg_launch_ms && n_launches && n_control_steps, "null argument");
-  long long st = 0;
-  h->e->base.bk.collect_timing(avg_launch_ms, n_launches, &st);
-  *n_control_steps = (int64_t)st;
-  LL_CATCH
-}
-int ll_epmc_set_actions(ll_epmc_engine* h, const float* h_actions) {
-  LL_TRY
-  LL_CHECK(h && h_actions, "null argument");
-  h->e->base.bk.sync();
-  h->e->base.bk.h2d(h->e->base.d_actions, h_actions, (size_t)h->e->base.P.n_envs * 12 * 4);
-  LL_CATCH
-}
+int ll_epmc_create(const ll_epmc_config* cfg, const double* model_blob, int blob_len, const double* init_state37, ll_epmc_engine** out) { return ll_create_as(out, cfg, model_blob, blob_len, init_state37); }
+int ll_epmc_destroy(ll_epmc_engine* h) { return ll_destroy_as(h); }
+int ll_epmc_reset(ll_epmc_engine* h, const int32_t* env_ids, int n, const float* h_draws, const float* h_prev_orn) { return ll_reset_as(h, env_ids, n, h_draws, h_prev_orn); }
+int ll_epmc_step(ll_epmc_engine* h, const float* d_actions) { return ll_step_as(h, d_actions); }
+int ll_epmc_step_random_n(ll_epmc_engine* h, float sigma, int n_steps) { return ll_step_random_n_as(h, sigma, n_steps); }
+int ll_epmc_kernel_time_stats(ll_epmc_engine* h, double* avg_launch_ms, int* n_launches, int64_t* n_control_steps) { return ll_kernel_time_stats_as(h, avg_launch_ms, n_launches, n_control_steps); }
+int ll_epmc_set_actions(ll_epmc_engine* h, const float* h_actions) { return ll_set_actions_as(h, h_actions); }
 int ll_epmc_step_scripted(ll_epmc_engine* h, const float* h_actions, const float* h_state, const uint8_t* h_ray_hit, const float* h_ray_frac,
                           const float* h_draws, int n_draws) {
   LL_TRY
@@ -68,68 +21,22 @@ int ll_epmc_step_scripted(ll_epmc_engine* h, const float* h_actions, const float
   h->e->step_scripted(h_actions, h_state, h_ray_hit, h_ray_frac, h_draws, n_draws);
   LL_CATCH
 }
-int ll_epmc_set_step_draws(ll_epmc_engine* h, const float* h_draws, int n_draws) {
-  LL_TRY
-  LL_CHECK(h && (h_draws || n_draws == 0), "null argument");
-  h->e->set_step_draws(h_draws, n_draws);
-  LL_CATCH
-}
+int ll_epmc_set_step_draws(ll_epmc_engine* h, const float* h_draws, int n_draws) { return ll_set_step_draws_as(h, h_draws, n_draws); }
 int ll_epmc_script_reset_rays(ll_epmc_engine* h, const uint8_t* h_ray_hit, const float* h_ray_frac) {
   LL_TRY
   LL_CHECK(h && h_ray_hit && h_ray_frac, "null argument");
   h->e->script_reset_rays(h_ray_hit, h_ray_frac);
   LL_CATCH
 }
-int ll_epmc_set_spec_param(ll_epmc_engine* h, int id, double value) {
-  LL_TRY
-  LL_CHECK(h, "null engine");
-  h->e->base.bk.sync();
-  std::string e = pmc_set_spec_param(h->e->base.P, id, value);
-  if (!e.empty()) throw PmcError(LL_EINVAL, e);
-  LL_CATCH
-}
-int ll_epmc_get_spec_param(ll_epmc_engine* h, int id, double* value) {
-  LL_TRY
-  LL_CHECK(h && value, "null argument");
-  LL_CHECK(id >= 0 && id < LLM_SPEC_COUNT, "unknown spec parameter id");
-  *value = pmc_get_spec_param(h->e->base.P, id);
-  LL_CATCH
-}
-int ll_epmc_sync(ll_epmc_engine* h) {
-  LL_TRY
-  LL_CHECK(h, "null engine");
-  h->e->base.bk.sync();
-  LL_CATCH
-}
-int ll_epmc_obs_dim(ll_epmc_engine* h) { return h ? h->e->base.P.obs_dim : LL_EINVAL; }
+int ll_epmc_set_spec_param(ll_epmc_engine* h, int id, double value) { return ll_set_spec_param_as(h, id, value); }
+int ll_epmc_get_spec_param(ll_epmc_engine* h, int id, double* value) { return ll_get_spec_param_as(h, id, value); }
+int ll_epmc_sync(ll_epmc_engine* h) { return ll_sync_as(h); }
+int ll_epmc_obs_dim(ll_epmc_engine* h) { return ll_obs_dim_as(h); }
 
-int ll_epmc_get_obs(ll_epmc_engine* h, float* h_obs) {
-  LL_TRY
-  LL_CHECK(h && h_obs, "null argument");
-  h->e->base.get_vec(h->e->base.P.obs, h_obs, (size_t)h->e->base.P.n_envs * h->e->base.P.obs_dim);
-  LL_CATCH
-}
-int ll_epmc_get_reward_done(ll_epmc_engine* h, float* h_reward, uint8_t* h_done, uint8_t* h_done_reason) {
-  LL_TRY
-  LL_CHECK(h, "null engine");
-  const size_t N = h->e->base.P.n_envs;
-  if (h_reward) h->e->base.get_vec(h->e->base.P.reward, h_reward, N);
-  if (h_done) h->e->base.get_vec(h->e->base.P.done, h_done, N);
-  if (h_done_reason) h->e->base.get_vec(h->e->base.P.done_reason, h_done_reason, N);
-  LL_CATCH
-}
-int ll_epmc_get_state(ll_epmc_engine* h, float* h_state37) {
-  LL_TRY
-  LL_CHECK(h && h_state37, "null argument");
-  h->e->base.get_soa(h->e->base.P.state, 37, h_state37);
-  LL_CATCH
-}
-int ll_epmc_set_state(ll_epmc_engine* h, const float* h_state37) {
-  LL_TRY
-  LL_CHECK(h && h_state37, "null argument");
-  h->e->base.set_soa(h->e->base.P.state, 37, h_state37);
-  LL_CATCH
-}
+int ll_epmc_get_obs(ll_epmc_engine* h, float* h_obs) { return ll_get_obs_as(h, h_obs); }
+int ll_epmc_get_reward_done(ll_epmc_engine* h, float* h_reward, uint8_t* h_done, uint8_t* h_done_reason) { return ll_get_reward_done_as(h, h_reward, h_done, h_done_reason); }
+int ll_epmc_get_state(ll_epmc_engine* h, float* h_state37) { return ll_get_state_as(h, h_state37); }
+int ll_epmc_set_state(ll_epmc_engine* h, const float* h_state37) { return ll_set_state_as(h, h_state37); }
 int ll_epmc_get_episode(ll_epmc_engine* h, float* h_rows19) {
   LL_TRY
   LL_CHECK(h && h_rows19, "null argument");
@@ -158,66 +65,12 @@ int ll_epmc_get_statics(ll_epmc_engine* h, float* h_rows, int32_t* h_count) {
   for (size_t e = 0; e < N; e++) h_count[e] = (int32_t)ep[e * EPMC_EP_STRIDE + EP_N_STATICS];
   LL_CATCH
 }
-int ll_epmc_get_rays(ll_epmc_engine* h, float* h_from, float* h_to, uint8_t* h_hit, float* h_frac) {
-  LL_TRY
-  LL_CHECK(h, "null engine");
-  if (!h->e->E.ray_trace) throw PmcError(LL_ESTATE, "the ray trace is kept for engines of at most 512 envs");
-  const size_t N = h->e->base.P.n_envs, R = EPMC_N_RAYS;
-  std::vector<float> tr(N * R * 8);
-  h->e->base.get_vec(h->e->E.ray_trace, tr.data(), tr.size());
-  for (size_t i = 0; i < N * R; i++) {
-    for (int k = 0; k < 3; k++) {
-      if (h_from) h_from[i * 3 + k] = tr[i * 8 + k];
-      if (h_to) h_to[i * 3 + k] = tr[i * 8 + 3 + k];
-    }
-    if (h_hit) h_hit[i] = tr[i * 8 + 6] > 0.5f;
-    if (h_frac) h_frac[i] = tr[i * 8 + 7];
-  }
-  LL_CATCH
-}
-int ll_epmc_get_push_trace(ll_epmc_engine* h, float* h_rows, int32_t* n_sub) {
-  LL_TRY
-  LL_CHECK(h && h_rows, "null argument");
-  h->e->base.get_vec(h->e->E.push_trace, h_rows, (size_t)h->e->base.P.n_envs * h->e->base.P.n_sub * 4);
-  if (n_sub) *n_sub = h->e->base.P.n_sub;
-  LL_CATCH
-}
-int ll_epmc_get_counters(ll_epmc_engine* h, uint64_t* steps, uint64_t* episodes, uint64_t* nonfinite) {
-  LL_TRY
-  LL_CHECK(h, "null engine");
-  unsigned long long c[4];
-  h->e->base.get_vec(h->e->base.P.counters, c, 4);
-  if (steps) *steps = (uint64_t)h->e->base.P.step_count * (uint64_t)h->e->base.P.n_envs;
-  if (episodes) *episodes = c[1];
-  if (nonfinite) *nonfinite = c[2];
-  LL_CATCH
-}
-int ll_epmc_device_ptrs(ll_epmc_engine* h, ll_device_ptrs_t* out) {
-  LL_TRY
-  LL_CHECK(h && out, "null argument");
-  const StepParams& P = h->e->base.P;
-  out->obs = P.obs; out->reward = P.reward; out->done = P.done; out->done_reason = P.done_reason;
-  out->actions = h->e->base.d_actions; out->terminal_obs = nullptr; out->obs_dim = P.obs_dim; out->n_envs = P.n_envs;
-  out->stream = h->e->base.bk.stream_handle();
-  LL_CATCH
-}
-int ll_epmc_enable_kernel_timing(ll_epmc_engine* h, int on) {
-  LL_TRY
-  LL_CHECK(h, "null engine");
-  h->e->base.bk.enable_timing(on != 0);
-  LL_CATCH
-}
-int ll_epmc_kernel_time_ms(ll_epmc_engine* h, double* avg_ms, int* n) {
-  LL_TRY
-  LL_CHECK(h && avg_ms && n, "null argument");
-  h->e->base.bk.collect_timing(avg_ms, n);
-  LL_CATCH
-}
-int ll_epmc_fill_random_actions(ll_epmc_engine* h, float sigma) {
-  LL_TRY
-  LL_CHECK(h, "null engine");
-  h->e->base.bk.launch_actions(h->e->base.P, h->e->base.d_actions, sigma);
-  LL_CATCH
-}
+int ll_epmc_get_rays(ll_epmc_engine* h, float* h_from, float* h_to, uint8_t* h_hit, float* h_frac) { return ll_get_rays_as(h, h_from, h_to, h_hit, h_frac, "the ray trace is kept for engines of at most 512 envs"); }
+int ll_epmc_get_push_trace(ll_epmc_engine* h, float* h_rows, int32_t* n_sub) { return ll_get_push_trace_as(h, h_rows, n_sub); }
+int ll_epmc_get_counters(ll_epmc_engine* h, uint64_t* steps, uint64_t* episodes, uint64_t* nonfinite) { return ll_get_counters_as(h, steps, episodes, nonfinite, 1); }
+int ll_epmc_device_ptrs(ll_epmc_engine* h, ll_device_ptrs_t* out) { return ll_device_ptrs_as(h, out, false); }
+int ll_epmc_enable_kernel_timing(ll_epmc_engine* h, int on) { return ll_enable_kernel_timing_as(h, on); }
+int ll_epmc_kernel_time_ms(ll_epmc_engine* h, double* avg_ms, int* n) { return ll_kernel_time_ms_as(h, avg_ms, n); }
+int ll_epmc_fill_random_actions(ll_epmc_engine* h, float sigma) { return ll_fill_random_actions_as(h, sigma); }
 
 }  // extern "C"

@@ -6,6 +6,7 @@
 
 #include "../../include/llenv_epmc.h"
 #include "epmc_step.hpp"
+#include "play_host.hpp"
 #include "pmc_engine.hpp"
 
 template <class BK>
@@ -19,21 +20,7 @@ struct EpmcEngine {
   int scr_draws_cap = 0;
   bool reset_rays_scripted = false;
 
-  static ll_config base_config(const ll_epmc_config& c) {
-    ll_config b;
-    memset(&b, 0, sizeof b);
-    b.abi_version = LL_ABI_VERSION;
-    b.n_envs = c.n_envs; b.device = c.device; b.auto_reset = c.auto_reset;
-    b.control_freq = c.control_freq; b.sim_freq = 500.0;                   // PGE:82 time_step = 1/500, not configurable
-    b.kp = c.kp; b.kd = c.kd; b.max_tau = c.max_tau;
-    b.foot_lateral_friction = c.friction_range[0];                         // per-episode value travels in SubstepExtra
-    for (int i = 0; i < 5; i++) { b.reward_weights[i] = 1.0; b.prop_order[i] = c.prop_order[i]; }
-    b.solver_iterations = c.solver_iterations;
-    b.seed = c.seed;
-    return b;
-  }
-
-  EpmcEngine(const ll_epmc_config& c, const double* blob, int blob_len, const double* init37) : base(base_config(c), blob, blob_len), cfg(c) {
+  EpmcEngine(const ll_epmc_config& c, const double* blob, int blob_len, const double* init37) : base(play_base_config(c, c.n_envs), blob, blob_len), cfg(c) {
     if (c.abi_version != LL_ABI_VERSION) throw PmcError(LL_EINVAL, "ll_epmc_config.abi_version mismatch");
     if (c.element_id < 0 || c.element_id > 3) throw PmcError(LL_EINVAL, "Unknown element id.");                 // BSE:249-250
     if (c.max_steps <= 0 || c.cmd_vary_freq_range[0] <= 0 || c.cmd_vary_freq_range[1] <= c.cmd_vary_freq_range[0])
@@ -45,24 +32,14 @@ struct EpmcEngine {
     P.obs_dim = 3 * P.prop_dim + 36 + LLE_OBS_DIM_FIXED;
     P.obs = base.template dalloc<float>(N * P.obs_dim);
     memset(&E, 0, sizeof E);
-    E.element_id = c.element_id; E.max_steps = c.max_steps;
-    E.push_enabled = c.push_enabled ? 1 : 0; E.push_count0 = c.push_count0;
-    E.push_interval_step = c.push_interval_step; E.push_duration_step = c.push_duration_step;
+    play_fill_params(E, c);
+    E.element_id = c.element_id;
     E.cmd_freq_lo = c.cmd_vary_freq_range[0]; E.cmd_freq_hi = c.cmd_vary_freq_range[1];
-    E.friction_lo = (float)c.friction_range[0]; E.friction_hi = (float)c.friction_range[1];
-    E.hforce_lo = (float)c.horizontal_force[0]; E.hforce_hi = (float)c.horizontal_force[1];
-    E.vforce_lo = (float)c.vertical_force[0]; E.vforce_hi = (float)c.vertical_force[1];
-    E.push_ratio = (float)c.push_strength_ratio; E.plane_friction = (float)LLM_PLANE_FRICTION;
     E.spd_lo = (float)c.target_spd_range[0]; E.spd_hi = (float)c.target_spd_range[1];
     E.aux_radius = (float)c.auxiliary_radius;
     E.hole_gap_lo = (float)c.hole_gap_height[0]; E.hole_gap_hi = (float)c.hole_gap_height[1];
-    E.box_friction = 0.5f; E.terrain_contacts = 1;
-    for (int i = 0; i < 4; i++) { E.noise_on[i] = c.noise_enabled[i] ? 1 : 0; E.noise_lo[i] = (float)c.noise_range[i][0]; E.noise_hi[i] = (float)c.noise_range[i][1]; }
     float init[37];
-    for (int i = 0; i < 37; i++) init[i] = (float)init37[i];
-    float* d_init = base.template dalloc<float>(37);
-    base.bk.h2d(d_init, init, sizeof init);
-    E.init_state = d_init;
+    play_upload_init(base, E, init37, init);
     E.ep = base.template dalloc<float>(N * EPMC_EP_STRIDE);
     E.info = base.template dalloc<float>(N * 6);
     E.statics = base.template dalloc<float>(N * EPMC_MAX_STATICS * 8);
@@ -120,14 +97,8 @@ struct EpmcEngine {
     have_reset = true;
   }
 
-  int pending_step_draws = 0;
-  void set_step_draws(const float* h_draws, int n_draws) {
-    if (n_draws < 0) throw PmcError(LL_EINVAL, "negative draw count");
-    ensure_script_buffers(n_draws);
-    base.bk.sync();
-    if (n_draws > 0) base.bk.h2d(d_scr_draws, h_draws, (size_t)base.P.n_envs * n_draws * 4);
-    pending_step_draws = n_draws > 0 ? n_draws : -1;              // -1: the step must not draw at all
-  }
+  int pending_step_draws = 0;      // (play_host.hpp play_set_step_draws goes by the names ensure_script_buffers, d_scr_draws, pending_step_draws)
+  void set_step_draws(const float* h_draws, int n_draws) { play_set_step_draws(*this, h_draws, n_draws, (size_t)base.P.n_envs); }
   void step(const float* d_act) {
     if (!have_reset) throw PmcError(LL_ESTATE, "ll_epmc_reset must be called before ll_epmc_step");
     base.need_launchable(LL_ENGINE_EPMC);

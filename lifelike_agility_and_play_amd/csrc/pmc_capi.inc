@@ -29,35 +29,17 @@ static thread_local std::string g_ll_err;
 #define LL_CHECK(c, msg) \
   if (!(c)) throw PmcError(LL_EINVAL, msg)
 
+#include "capi_shared.inc"
+
 extern "C" {
 
 const char* ll_last_error(void) { return g_ll_err.c_str(); }
 int ll_abi_version(void) { return LL_ABI_VERSION; }
 int ll_model_blob_len(void) { return LLM_BLOB_LEN; }
 
-int ll_create(const ll_config* cfg, const double* model_blob, int blob_len, ll_engine** out) {
-  LL_TRY
-  LL_CHECK(cfg && model_blob && out, "null argument");
-  *out = nullptr;
-  ll_engine* h = new ll_engine;
-  try {
-    h->e = new ENGINE(*cfg, model_blob, blob_len);
-  } catch (...) {
-    delete h;
-    throw;
-  }
-  *out = h;
-  LL_CATCH
-}
+int ll_create(const ll_config* cfg, const double* model_blob, int blob_len, ll_engine** out) { return ll_create_as(out, cfg, model_blob, blob_len); }
 
-int ll_destroy(ll_engine* h) {
-  LL_TRY
-  if (h) {
-    delete h->e;
-    delete h;
-  }
-  LL_CATCH
-}
+int ll_destroy(ll_engine* h) { return ll_destroy_as(h); }
 
 int ll_load_mocap(ll_engine* h, const float* h_frames, const int32_t* h_clip_len, int n_clips, double frame_step) {
   LL_TRY
@@ -85,19 +67,9 @@ int ll_load_obstacles(ll_engine* h, const int32_t* h_count, const double* h_tabl
   LL_CATCH
 }
 
-int ll_reset(ll_engine* h, const int32_t* h_env_ids, int n, const int32_t* h_clip_idx, const double* h_t0) {
-  LL_TRY
-  LL_CHECK(h, "null engine");
-  h->e->reset(h_env_ids, n, h_clip_idx, h_t0);
-  LL_CATCH
-}
+int ll_reset(ll_engine* h, const int32_t* h_env_ids, int n, const int32_t* h_clip_idx, const double* h_t0) { return ll_reset_as(h, h_env_ids, n, h_clip_idx, h_t0); }
 
-int ll_step(ll_engine* h, const float* d_actions) {
-  LL_TRY
-  LL_CHECK(h, "null engine");
-  h->e->step(d_actions);
-  LL_CATCH
-}
+int ll_step(ll_engine* h, const float* d_actions) { return ll_step_as(h, d_actions); }
 
 int ll_step_scripted(ll_engine* h, const float* d_actions, const float* h_state, const float* h_feet) {
   LL_TRY
@@ -114,21 +86,8 @@ int ll_probe_pd_torque(ll_engine* h, const float* h_rows, int n, int mode, float
   LL_CATCH
 }
 
-int ll_set_spec_param(ll_engine* h, int id, double value) {
-  LL_TRY
-  LL_CHECK(h, "null engine");
-  h->e->bk.sync();
-  std::string e = pmc_set_spec_param(h->e->P, id, value);
-  if (!e.empty()) throw PmcError(LL_EINVAL, e);
-  LL_CATCH
-}
-int ll_get_spec_param(ll_engine* h, int id, double* value) {
-  LL_TRY
-  LL_CHECK(h && value, "null argument");
-  LL_CHECK(id >= 0 && id < LLM_SPEC_COUNT, "unknown spec parameter id");
-  *value = pmc_get_spec_param(h->e->P, id);
-  LL_CATCH
-}
+int ll_set_spec_param(ll_engine* h, int id, double value) { return ll_set_spec_param_as(h, id, value); }
+int ll_get_spec_param(ll_engine* h, int id, double* value) { return ll_get_spec_param_as(h, id, value); }
 
 int ll_fill_random_actions(ll_engine* h, float sigma) {
   LL_TRY
@@ -144,19 +103,9 @@ int ll_step_random(ll_engine* h, float sigma) {
   LL_CATCH
 }
 
-int ll_step_random_n(ll_engine* h, float sigma, int n_steps) {
-  LL_TRY
-  LL_CHECK(h, "null engine");
-  h->e->step_random_n(sigma, n_steps);
-  LL_CATCH
-}
+int ll_step_random_n(ll_engine* h, float sigma, int n_steps) { return ll_step_random_n_as(h, sigma, n_steps); }
 
-int ll_sync(ll_engine* h) {
-  LL_TRY
-  LL_CHECK(h, "null engine");
-  h->e->bk.sync();
-  LL_CATCH
-}
+int ll_sync(ll_engine* h) { return ll_sync_as(h); }
 
 int ll_set_stream(ll_engine* h, void* hip_stream) {
   LL_TRY
@@ -200,22 +149,9 @@ int ll_finish_unroll(ll_engine* h, int buffer, float gamma, float lam, const flo
   LL_CATCH
 }
 
-int ll_device_ptrs(ll_engine* h, ll_device_ptrs_t* out) {
-  LL_TRY
-  LL_CHECK(h && out, "null argument");
-  const StepParams& P = h->e->P;
-  out->obs = P.obs; out->reward = P.reward; out->done = P.done; out->done_reason = P.done_reason;
-  out->actions = h->e->d_actions; out->terminal_obs = P.term_obs;
-  out->obs_dim = P.obs_dim; out->n_envs = P.n_envs; out->stream = h->e->bk.stream_handle();
-  LL_CATCH
-}
+int ll_device_ptrs(ll_engine* h, ll_device_ptrs_t* out) { return ll_device_ptrs_as(h, out, true); }
 
-int ll_get_obs(ll_engine* h, float* h_obs) {
-  LL_TRY
-  LL_CHECK(h && h_obs, "null argument");
-  h->e->get_vec(h->e->P.obs, h_obs, (size_t)h->e->P.n_envs * h->e->P.obs_dim);
-  LL_CATCH
-}
+int ll_get_obs(ll_engine* h, float* h_obs) { return ll_get_obs_as(h, h_obs); }
 int ll_get_terminal_obs(ll_engine* h, float* h_obs) {
   LL_TRY
   LL_CHECK(h && h_obs, "null argument");
@@ -224,36 +160,12 @@ int ll_get_terminal_obs(ll_engine* h, float* h_obs) {
   LL_CATCH
 }
 
-int ll_get_reward_done(ll_engine* h, float* h_reward, uint8_t* h_done, uint8_t* h_done_reason) {
-  LL_TRY
-  LL_CHECK(h, "null engine");
-  const size_t N = h->e->P.n_envs;
-  if (h_reward) h->e->get_vec(h->e->P.reward, h_reward, N);
-  if (h_done) h->e->get_vec(h->e->P.done, h_done, N);
-  if (h_done_reason) h->e->get_vec(h->e->P.done_reason, h_done_reason, N);
-  LL_CATCH
-}
+int ll_get_reward_done(ll_engine* h, float* h_reward, uint8_t* h_done, uint8_t* h_done_reason) { return ll_get_reward_done_as(h, h_reward, h_done, h_done_reason); }
 
-int ll_set_actions(ll_engine* h, const float* h_actions) {
-  LL_TRY
-  LL_CHECK(h && h_actions, "null argument");
-  h->e->bk.sync();
-  h->e->bk.h2d(h->e->d_actions, h_actions, (size_t)h->e->P.n_envs * 12 * 4);
-  LL_CATCH
-}
+int ll_set_actions(ll_engine* h, const float* h_actions) { return ll_set_actions_as(h, h_actions); }
 
-int ll_get_state(ll_engine* h, float* h_state) {
-  LL_TRY
-  LL_CHECK(h && h_state, "null argument");
-  h->e->get_soa(h->e->P.state, 37, h_state);
-  LL_CATCH
-}
-int ll_set_state(ll_engine* h, const float* h_state) {
-  LL_TRY
-  LL_CHECK(h && h_state, "null argument");
-  h->e->set_soa(h->e->P.state, 37, h_state);
-  LL_CATCH
-}
+int ll_get_state(ll_engine* h, float* h_state) { return ll_get_state_as(h, h_state); }
+int ll_set_state(ll_engine* h, const float* h_state) { return ll_set_state_as(h, h_state); }
 int ll_get_ref_state(ll_engine* h, float* h_state) {
   LL_TRY
   LL_CHECK(h && h_state, "null argument");
@@ -305,17 +217,7 @@ int ll_get_feet(ll_engine* h, float* h_feet_dyn, float* h_feet_ref) {
   LL_CATCH
 }
 
-int ll_get_counters(ll_engine* h, uint64_t* steps, uint64_t* episodes, uint64_t* nonfinite) {
-  LL_TRY
-  LL_CHECK(h, "null engine");
-  unsigned long long c[4];
-  h->e->get_vec(h->e->P.counters, c, 4);
-  c[0] = (unsigned long long)h->e->P.step_count * (unsigned long long)h->e->P.n_envs;
-  if (steps) *steps = c[0];
-  if (episodes) *episodes = c[1];
-  if (nonfinite) *nonfinite = c[2];
-  LL_CATCH
-}
+int ll_get_counters(ll_engine* h, uint64_t* steps, uint64_t* episodes, uint64_t* nonfinite) { return ll_get_counters_as(h, steps, episodes, nonfinite, 1); }
 
 int ll_get_table_sync(ll_engine* h, uint64_t* stale_reseeds) {
   LL_TRY
@@ -345,25 +247,8 @@ int ll_debug_timestamps(ll_engine* h, uint64_t* out) {
 }
 #endif
 
-int ll_enable_kernel_timing(ll_engine* h, int on) {
-  LL_TRY
-  LL_CHECK(h, "null engine");
-  h->e->bk.enable_timing(on != 0);
-  LL_CATCH
-}
-int ll_kernel_time_ms(ll_engine* h, double* avg_ms, int* n_launches) {
-  LL_TRY
-  LL_CHECK(h && avg_ms && n_launches, "null argument");
-  h->e->bk.collect_timing(avg_ms, n_launches);
-  LL_CATCH
-}
-int ll_kernel_time_stats(ll_engine* h, double* avg_launch_ms, int* n_launches, int64_t* n_control_steps) {
-  LL_TRY
-  LL_CHECK(h && avg_launch_ms && n_launches && n_control_steps, "null argument");
-  long long st = 0;
-  h->e->bk.collect_timing(avg_launch_ms, n_launches, &st);
-  *n_control_steps = (int64_t)st;
-  LL_CATCH
-}
+int ll_enable_kernel_timing(ll_engine* h, int on) { return ll_enable_kernel_timing_as(h, on); }
+int ll_kernel_time_ms(ll_engine* h, double* avg_ms, int* n_launches) { return ll_kernel_time_ms_as(h, avg_ms, n_launches); }
+int ll_kernel_time_stats(ll_engine* h, double* avg_launch_ms, int* n_launches, int64_t* n_control_steps) { return ll_kernel_time_stats_as(h, avg_launch_ms, n_launches, n_control_steps); }
 
 }  // extern "C"

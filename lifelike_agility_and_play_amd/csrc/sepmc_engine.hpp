@@ -5,6 +5,7 @@
 #include <string.h>
 
 #include "../../include/llenv_sepmc.h"
+#include "play_host.hpp"
 #include "pmc_engine.hpp"
 #include "sepmc_step.hpp"
 
@@ -17,23 +18,9 @@ struct SepmcEngine {
   float *d_scr_state = nullptr, *d_scr_frac = nullptr, *d_scr_draws = nullptr, *d_reset_draws = nullptr, *d_prev_orn = nullptr;
   uint8_t *d_scr_hit = nullptr, *d_scr_vis = nullptr;
   int32_t *d_scr_contacts = nullptr, *d_row_ids = nullptr;
-  int scr_draws_cap = 0, pending_step_draws = 0;
+  int scr_draws_cap = 0, pending_step_draws = 0;      // (play_host.hpp play_set_step_draws goes by the names ensure_script_buffers, d_scr_draws, pending_step_draws)
 
-  static ll_config base_config(const ll_sepmc_config& c) {
-    ll_config b;
-    memset(&b, 0, sizeof b);
-    b.abi_version = LL_ABI_VERSION;
-    b.n_envs = 2 * c.n_arenas; b.device = c.device; b.auto_reset = c.auto_reset;
-    b.control_freq = c.control_freq; b.sim_freq = 500.0;                   // CTG:53
-    b.kp = c.kp; b.kd = c.kd; b.max_tau = c.max_tau;
-    b.foot_lateral_friction = c.friction_range[0];
-    for (int i = 0; i < 5; i++) { b.reward_weights[i] = 1.0; b.prop_order[i] = c.prop_order[i]; }
-    b.solver_iterations = c.solver_iterations;
-    b.seed = c.seed;
-    return b;
-  }
-
-  SepmcEngine(const ll_sepmc_config& c, const double* blob, int blob_len, const double* init37) : base(base_config(c), blob, blob_len), cfg(c) {
+  SepmcEngine(const ll_sepmc_config& c, const double* blob, int blob_len, const double* init37) : base(play_base_config(c, 2 * c.n_arenas), blob, blob_len), cfg(c) {
     if (c.abi_version != LL_ABI_VERSION) throw PmcError(LL_EINVAL, "ll_sepmc_config.abi_version mismatch");
     if (c.n_arenas <= 0 || c.max_steps <= 0) throw PmcError(LL_EINVAL, "bad n_arenas / max_steps");
     if (c.push_enabled && (c.push_interval_step <= 0 || c.push_duration_step > c.push_interval_step))
@@ -44,20 +31,10 @@ struct SepmcEngine {
     P.obs = base.template dalloc<float>(N * P.obs_dim);
     memset(&S, 0, sizeof S);
     EpmcParams& E = S.e;
-    E.max_steps = c.max_steps;
-    E.push_enabled = c.push_enabled ? 1 : 0; E.push_count0 = c.push_count0;
-    E.push_interval_step = c.push_interval_step; E.push_duration_step = c.push_duration_step;
-    E.friction_lo = (float)c.friction_range[0]; E.friction_hi = (float)c.friction_range[1];
-    E.hforce_lo = (float)c.horizontal_force[0]; E.hforce_hi = (float)c.horizontal_force[1];
-    E.vforce_lo = (float)c.vertical_force[0]; E.vforce_hi = (float)c.vertical_force[1];
-    E.push_ratio = (float)c.push_strength_ratio; E.plane_friction = (float)LLM_PLANE_FRICTION;
-    E.aux_radius = -1.0f; E.box_friction = 0.5f; E.terrain_contacts = 1;
-    for (int i = 0; i < 4; i++) { E.noise_on[i] = c.noise_enabled[i] ? 1 : 0; E.noise_lo[i] = (float)c.noise_range[i][0]; E.noise_hi[i] = (float)c.noise_range[i][1]; }
+    play_fill_params(E, c);
+    E.aux_radius = -1.0f;
     float init[37];
-    for (int i = 0; i < 37; i++) init[i] = (float)init37[i];
-    float* d_init = base.template dalloc<float>(37);
-    base.bk.h2d(d_init, init, sizeof init);
-    E.init_state = d_init;
+    play_upload_init(base, E, init37, init);
     E.boxes = base.template dalloc<float>(N * EPMC_MAX_BOXES * EPMC_BOX_WORDS + EPMC_BOX_WORDS);   // + one record: the ray loops read one box ahead
     E.ray_pose = base.template dalloc<float>(N * EPMC_RAY_POSE);                                    // what the ray kernel needs of a row (epmc_step.hpp percept_rays; backends that cast the rays inside the step never touch it)
     E.push_trace = base.template dalloc<float>(N * P.n_sub * 4);
@@ -124,13 +101,7 @@ struct SepmcEngine {
     reset_scripted = false;
     have_reset = true;
   }
-  void set_step_draws(const float* h_draws, int n_draws) {
-    if (n_draws < 0) throw PmcError(LL_EINVAL, "negative draw count");
-    ensure_script_buffers(n_draws);
-    base.bk.sync();
-    if (n_draws > 0) base.bk.h2d(d_scr_draws, h_draws, (size_t)(base.P.n_envs / 2) * n_draws * 4);
-    pending_step_draws = n_draws > 0 ? n_draws : -1;
-  }
+  void set_step_draws(const float* h_draws, int n_draws) { play_set_step_draws(*this, h_draws, n_draws, (size_t)(base.P.n_envs / 2)); }
   void step(const float* d_act) {
     if (!have_reset) throw PmcError(LL_ESTATE, "ll_sepmc_reset must be called before ll_sepmc_step");
     base.need_launchable(LL_ENGINE_SEPMC);

@@ -20,17 +20,10 @@ _SIGS = {
     'll_policy_time_ms': (C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_int)]),
 }
 EXPORTED_SYMBOLS = sorted(_SIGS)
-_bound = {}
 
 
 def load_library(path=None):
-    lib = capi.load_library(path)
-    if id(lib) not in _bound:
-        for name, (res, args) in _SIGS.items():
-            fn = getattr(lib, name)
-            fn.restype, fn.argtypes = res, args
-        _bound[id(lib)] = True
-    return lib
+    return capi.bind(capi.load_library(path), _SIGS)
 
 
 def pack_weights(npz_path=DEFAULT_WEIGHTS):
@@ -40,17 +33,13 @@ def pack_weights(npz_path=DEFAULT_WEIGHTS):
     return np.ascontiguousarray(flat)
 
 
-class HipPmcPolicy(object):
-    def __init__(self, npz_path=DEFAULT_WEIGHTS, device=0, lib_path=None):
-        self.lib = load_library(lib_path)
-        w = pack_weights(npz_path)
-        self._pid = os.getpid()
-        self.h = C.c_void_p()
-        self._chk(self.lib.ll_policy_create(w.ctypes.data_as(C.c_void_p), int(w.size), int(device), C.byref(self.h)))
+class HipPmcPolicy(capi.NativeHandle):
+    _destroy = 'll_policy_destroy'
 
-    def _chk(self, rc):
-        if rc != 0:
-            raise capi.LLError(rc, self.lib.ll_last_error().decode())
+    def __init__(self, npz_path=DEFAULT_WEIGHTS, device=0, lib_path=None):
+        self._open(load_library(lib_path))
+        w = pack_weights(npz_path)
+        self._chk(self.lib.ll_policy_create(w.ctypes.data_as(C.c_void_p), int(w.size), int(device), C.byref(self.h)))
 
     def act_ptr(self, d_obs, d_actions, n_envs, stream=None, d_code=None):
         self._chk(self.lib.ll_policy_act(self.h, C.c_void_p(int(d_obs)), C.c_void_p(int(d_actions)), C.c_void_p(int(d_code)) if d_code else None,
@@ -78,15 +67,3 @@ class HipPmcPolicy(object):
         ms, n = C.c_double(0), C.c_int(0)
         self._chk(self.lib.ll_policy_time_ms(self.h, C.byref(ms), C.byref(n)))
         return ms.value, n.value
-
-    def close(self):
-        if getattr(self, 'h', None) is not None and self.h:
-            if getattr(self, '_pid', None) == os.getpid():      # (a fork()ed child inherits the object, not the HIP context: it must not destroy it)
-                self.lib.ll_policy_destroy(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:     # noqa: BLE001
-            pass

@@ -39,36 +39,28 @@ _SIGS = {
     'll_hl_league_plan_only': (C.c_int, [C.c_void_p, C.c_int]),
 }
 EXPORTED_SYMBOLS = sorted(_SIGS)
-_bound = {}
 
 
 def load_library(path=None):
-    lib = U.load_library(path)
-    if id(lib) not in _bound:
-        for name, (res, args) in _SIGS.items():
-            fn = getattr(lib, name)
-            fn.restype, fn.argtypes = res, args
-        _bound[id(lib)] = True
-    return lib
+    return capi.bind(U.load_library(path), _SIGS)
 
 
 row_layout = U.row_layout
 split_row = U.split_row
 
 
-class HlLeagueActor(object):
+class HlLeagueActor(capi.NativeHandle):
     """ll_hl_league over `engine` (a SepmcEngine created with auto_reset, or a game holding one as .engine), which must stay open while the
     league lives."""
+    _destroy = 'll_hl_league_destroy'
 
     def __init__(self, engine, n_opponents, unroll_length, n_buffers=2, lib_path=None):
         from ..sepmc_capi import SepmcEngine
-        self.lib = load_library(lib_path)
+        self._open(load_library(lib_path))
         eng = getattr(engine, 'engine', engine)
         if not isinstance(eng, SepmcEngine):
             raise TypeError('HlLeagueActor drives a SepmcEngine, not %r' % type(eng).__name__)
         self.engine = eng
-        self._pid = os.getpid()
-        self.h = C.c_void_p()
         self._chk(self.lib.ll_hl_league_create(eng.h, int(n_opponents), int(unroll_length), int(n_buffers), C.byref(self.h)))
         lay = U.LLHlUnrollLayout()
         self._chk(self.lib.ll_hl_league_layout(self.h, C.byref(lay)))
@@ -79,10 +71,6 @@ class HlLeagueActor(object):
         self.unroll_length, self.n_buffers = int(lay.unroll_length), int(lay.n_buffers)
         self.d_base, self.n_bytes = int(lay.d_base), int(lay.n_bytes)
         self.fields = {name: (int(lay.off[i]), int(lay.dim[i])) for i, name in enumerate(U.LLU_FIELDS)}
-
-    def _chk(self, rc):
-        if rc != 0:
-            raise capi.LLError(rc, self.lib.ll_last_error().decode())
 
     def set_weights(self, slot, weights, value_npz=None, value_weights=None):
         """A new model for `slot` (0: the learner, with its value branch; 1 .. n_opponents: an opponent, policy only), uploaded in the order of
@@ -150,15 +138,3 @@ class HlLeagueActor(object):
     def plan_only(self, n_launches):
         """n launches of the plan kernel that tally and draw nothing (for measuring)"""
         self._chk(self.lib.ll_hl_league_plan_only(self.h, int(n_launches)))
-
-    def close(self):
-        if getattr(self, 'h', None) is not None and self.h:
-            if getattr(self, '_pid', None) == os.getpid():      # (a fork()ed child inherits the object, not the HIP context: it must not destroy it)
-                self.lib.ll_hl_league_destroy(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:     # noqa: BLE001
-            pass

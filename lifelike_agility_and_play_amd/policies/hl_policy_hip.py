@@ -15,7 +15,6 @@ The PPO actor (ll_hl_policy_act_pg): every head sampled, its neglogp and the val
         engine.step()
 """
 import ctypes as C
-import os
 
 import numpy as np
 
@@ -48,17 +47,10 @@ _SIGS = {
     'll_hl_policy_time_ms': (C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_int)]),
 }
 EXPORTED_SYMBOLS = sorted(_SIGS)
-_bound = {}
 
 
 def load_library(path=None):
-    lib = capi.load_library(path)
-    if id(lib) not in _bound:
-        for name, (res, args) in _SIGS.items():
-            fn = getattr(lib, name)
-            fn.restype, fn.argtypes = res, args
-        _bound[id(lib)] = True
-    return lib
+    return capi.bind(capi.load_library(path), _SIGS)
 
 
 def pack_weights(kind, npz_path):
@@ -82,15 +74,13 @@ def _vp(x):
     return C.c_void_p(int(x)) if x else None
 
 
-class _HipHlPolicy(object):
-    KIND = None
+class _HipHlPolicy(capi.NativeHandle):
+    KIND, _destroy = None, 'll_hl_policy_destroy'
 
     def __init__(self, npz_path, max_rows, device=0, lib_path=None, weights=None, value_npz=None):
-        self.lib = load_library(lib_path)
+        self._open(load_library(lib_path))
         w = pack_weights(self.KIND, npz_path) if weights is None else np.ascontiguousarray(weights, dtype=np.float32)
         self.max_rows = int(max_rows)
-        self._pid = os.getpid()
-        self.h = C.c_void_p()
         self._chk(self.lib.ll_hl_policy_create(self.KIND, w.ctypes.data_as(C.c_void_p), int(w.size), self.max_rows, int(device), C.byref(self.h)))
         self.state_dim = int(self.lib.ll_hl_policy_state_dim(self.h))
         self.n_heads = N_HEADS[self.KIND]
@@ -114,10 +104,6 @@ class _HipHlPolicy(object):
             v = pack_value_weights(self.KIND, value_npz) if value_weights is None else np.ascontiguousarray(value_weights, dtype=np.float32)
         self._chk(self.lib.ll_hl_policy_set_weights(self.h, w.ctypes.data_as(C.c_void_p), int(w.size), v.ctypes.data_as(C.c_void_p) if v is not None else None,
                                                     int(v.size) if v is not None else 0, _vp(stream)))
-
-    def _chk(self, rc):
-        if rc != 0:
-            raise capi.LLError(rc, self.lib.ll_last_error().decode())
 
     def act_ptr(self, d_obs, d_actions, n_rows, stream=None, d_reset=None, d_code=None, d_heading=None, obs_stride=None):
         """ll_hl_policy_act on raw device addresses; asynchronous on `stream` (None: the default stream)."""
@@ -188,18 +174,6 @@ class _HipHlPolicy(object):
         ms, n = C.c_double(0), C.c_int(0)
         self._chk(self.lib.ll_hl_policy_time_ms(self.h, C.byref(ms), C.byref(n)))
         return ms.value, n.value
-
-    def close(self):
-        if getattr(self, 'h', None) is not None and self.h:
-            if getattr(self, '_pid', None) == os.getpid():      # (a fork()ed child inherits the object, not the HIP context: it must not destroy it)
-                self.lib.ll_hl_policy_destroy(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:     # noqa: BLE001
-            pass
 
 
 class HipEpmcPolicy(_HipHlPolicy):

@@ -9,7 +9,6 @@ control step: X, A, neglogp, R, V, r, discount, S, M -- the input tuple of the r
     f = split_row(rec.block(0))          # named torch views: f['X'] [n_rows][128][916], f['R'] [n_rows][128], ...
 """
 import ctypes as C
-import os
 
 from .. import capi
 from . import hl_policy_hip as H
@@ -36,17 +35,10 @@ _SIGS = {
     'll_hl_unroll_finish': (C.c_int, [C.c_void_p, C.c_int, C.c_float, C.c_float, C.c_void_p]),
 }
 EXPORTED_SYMBOLS = sorted(_SIGS)
-_bound = {}
 
 
 def load_library(path=None):
-    lib = H.load_library(path)
-    if id(lib) not in _bound:
-        for name, (res, args) in _SIGS.items():
-            fn = getattr(lib, name)
-            fn.restype, fn.argtypes = res, args
-        _bound[id(lib)] = True
-    return lib
+    return capi.bind(H.load_library(path), _SIGS)
 
 
 def row_layout(kind):
@@ -76,18 +68,17 @@ def split_row(block, layout=None):
     return out
 
 
-class HlUnrollRecorder(object):
+class HlUnrollRecorder(capi.NativeHandle):
     """ll_hl_unroll over `engine` (an EpmcEngine / SepmcEngine, or a game holding one as .engine) and `policy` (HipEpmcPolicy / HipSepmcPolicy with
     a value branch).  Both must stay open while the recorder lives."""
+    _destroy = 'll_hl_unroll_destroy'
 
     def __init__(self, engine, policy, unroll_length, n_buffers=2, lib_path=None):
         from ..epmc_capi import EpmcEngine
         from ..sepmc_capi import SepmcEngine
-        self.lib = load_library(lib_path)
+        self._open(load_library(lib_path))
         eng = getattr(engine, 'engine', engine)
         self.engine, self.policy = eng, policy
-        self._pid = os.getpid()
-        self.h = C.c_void_p()
         if isinstance(eng, EpmcEngine):
             create = self.lib.ll_hl_unroll_create_epmc
         elif isinstance(eng, SepmcEngine):
@@ -102,10 +93,6 @@ class HlUnrollRecorder(object):
         self.unroll_length, self.n_buffers = int(lay.unroll_length), int(lay.n_buffers)
         self.d_base, self.n_bytes = int(lay.d_base), int(lay.n_bytes)
         self.fields = {name: (int(lay.off[i]), int(lay.dim[i])) for i, name in enumerate(LLU_FIELDS)}
-
-    def _chk(self, rc):
-        if rc != 0:
-            raise capi.LLError(rc, self.lib.ll_last_error().decode())
 
     def steps(self, seed, n_steps, sample=True):
         """n_steps x { act_pg ; step } recorded, queued on the engine's stream; the Philox step index is the recorder's own step count."""
@@ -133,15 +120,3 @@ class HlUnrollRecorder(object):
 
     def split_row(self, block):
         return split_row(block, self.fields)
-
-    def close(self):
-        if getattr(self, 'h', None) is not None and self.h:
-            if getattr(self, '_pid', None) == os.getpid():      # (a fork()ed child inherits the object, not the HIP context: it must not destroy it)
-                self.lib.ll_hl_unroll_destroy(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:     # noqa: BLE001
-            pass

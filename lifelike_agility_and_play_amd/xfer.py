@@ -34,17 +34,10 @@ _SIGS = {
     'll_xfer_set_device': (C.c_int, [C.c_int]),
 }
 EXPORTED_SYMBOLS = sorted(_SIGS)
-_bound = {}
 
 
 def load_library(path=None):
-    lib = capi.load_library(path)
-    if id(lib) not in _bound:
-        for name, (res, args) in _SIGS.items():
-            fn = getattr(lib, name)
-            fn.restype, fn.argtypes = res, args
-        _bound[id(lib)] = True
-    return lib
+    return capi.bind(capi.load_library(path), _SIGS)
 
 
 def _chk(lib, rc):
