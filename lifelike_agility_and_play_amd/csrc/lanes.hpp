@@ -107,6 +107,7 @@ struct GpuLanes {
 
   static constexpr bool kHoldLink = false;   // pmc_step.hpp own_link: re-read the own-link constants every substep
   static constexpr bool kPrefetchShapes = false;   // see WithShapePrefetch below
+  static constexpr bool kSubPlan = false;          // see WithSubPlan below
   LL_D GpuLanes(float* lds) : leg_((threadIdx.x >> 2) & 3), sub_(threadIdx.x & 3), lane16_(threadIdx.x & 15), lds_(lds), cbase_(0), tbase_(0) {}
 
   // Stage the constant tables in LDS: legc [n_leg_fields][4] then candc [n_cand_words][16].  A constant then costs one
@@ -788,6 +789,27 @@ template <class Base>
 struct WithConeInLds : Base {
   using Base::Base;
   static constexpr bool kConeInLds = true;
+};
+
+// The step resolves what its substeps branch on into a SubPlan (pmc_params.hpp) and the substeps test bits of it instead of fetching arguments.  Per kernel by A/B on one box
+// (profiles/substep_plan_ab.txt): the multi-step one-wave-per-SIMD PMC kernel gains, the single-step kernels lose 0.6 % and stay as they were.
+template <class Base, bool ON>
+struct WithSubPlan : Base {
+  using Base::Base;
+  static constexpr bool kSubPlan = ON;
+};
+
+// The sixteen turn masks of a substep's solve as sixteen compares of the lane id instead of sixteen 64-bit constants: the compiler parks the constants in a spill register once
+// per control step and copies them back per substep (eight lane reads, eight lane writes, thirty scalar moves).  The masks only ever select in a v_cndmask under the same EXEC,
+// so that a compare leaves the bits of lanes which sit the step out at 0 changes nothing.  The lane id is taken afresh, or the compares would be hoisted and parked likewise.
+template <class Base>
+struct WithTurnMasksCmp : Base {
+  using Base::Base;
+  LL_D void prepare_turn_masks() const {
+    int l16 = this->lane16_;
+    asm volatile("" : "+v"(l16));
+    for (int t = 0; t < 16; t++) this->tm_[t] = __builtin_amdgcn_uicmpl(l16, t, 32);      // 32: equal
+  }
 };
 
 #define LL_FMAC_RBCAST(L_)                                                                                               \

@@ -101,7 +101,12 @@ enum BaseConst {
 #define PMC_PGS_HOIST_TERRAIN 0   // 1: the one-wave-per-SIMD playground build too (measured: no difference; its 256-register build has the copies, - 9 % at 65536 envs)
 #endif
 
-#define LL_MAX_STEPS_PER_LAUNCH 128   // control steps one launch of ll_step_random_n runs at most (longer calls are split); sizes the per-step table slots
+#ifndef PMC_SUB_PLAN
+#define PMC_SUB_PLAN 1            // pmc_step.hpp: what the substep BRANCHES on (SubPlan below) is resolved once per control step into two words and tested as bits, in the kernels whose lane policy asks for it
+                                  // (lanes.hpp WithSubPlan; llenv.hip says which: decided per kernel by A/B).  0: every test fetches its argument, as before
+#endif
+
+#define LL_MAX_STEPS_PER_LAUNCH 128  // control steps one launch of ll_step_random_n runs at most (longer calls are split); sizes the per-step table slots
 
 struct StepParams {
   static constexpr bool kFirstKernelArgument = true;   // every kernel takes it first, by value: lanes.hpp WithParamsReload re-reads it from the kernarg segment
@@ -199,6 +204,35 @@ struct StepParams {
   const float* candc;       // [CAND_TABLE_WORDS][16]
   const float* basec;       // [BC_COUNT]
 };
+
+// The substep plan (PMC_SUB_PLAN): every argument the substep only BRANCHES on is wave-uniform and fixed for a control step, so the step resolves them once, where it re-reads
+// the argument block anyway (lanes.hpp WithParamsReload level 1), and the ten substeps test bits of one word instead of fetching an argument and waiting for it ahead of each
+// branch (a lone wave pays ~58 ticks for s_load + s_waitcnt + s_cmp + s_cbranch on a warm line against ~19 with the word at hand and ~38 from a spilled lane:
+// tools/issue_probe.hip, profiles/scalar_wait_probe.txt).  Made per control step, never per launch: a spec set between two steps acts as it always has.  The counts are stored
+// clamped to the range the substep's loops can reach, which decides every `slot >= count` test the way the argument itself does.
+// PMC_PLAN_FRESH: the substep takes the two words as values the compiler knows nothing about, so that a test stays a bit test next to its branch; left to itself the compiler
+// forms every test once per control step as a 64-bit lane mask and parks the ten pairs in a spill register (two lane reads ahead of each branch: more than the fetch cost).
+#if defined(__HIP_DEVICE_COMPILE__)
+#define PMC_PLAN_FRESH(x) asm volatile("" : "+s"(x))
+#else
+#define PMC_PLAN_FRESH(x) do { } while (0)
+#endif
+struct SubPlan {
+  enum : uint32_t { MC_MASK = 7u, MS_SHIFT = 3, MS_MASK = 3u, SELF_COLLISION = 1u << 5, FRICTION_DIRS = 1u << 6, LIMIT_SPECULATIVE = 1u << 7, ERP_DEEP = 1u << 8, LIMIT_ERP_DEEP = 1u << 9 };
+  uint32_t w;
+  int32_t n_iter;
+  LL_HD int max_contacts() const { return (int)(w & MC_MASK); }
+  LL_HD int max_self() const { return (int)((w >> MS_SHIFT) & MS_MASK); }
+  LL_HD bool has(uint32_t bit) const { return (w & bit) != 0; }
+};
+LL_HD SubPlan pmc_sub_plan(const StepParams& P) {
+  SubPlan pl;
+  const int mc = P.max_contacts < 0 ? 0 : (P.max_contacts > PMC_K ? PMC_K : P.max_contacts), ms = P.max_self < 0 ? 0 : (P.max_self > 2 ? 2 : P.max_self);
+  pl.w = (uint32_t)mc | ((uint32_t)ms << SubPlan::MS_SHIFT) | (P.self_collision > 0.5f ? SubPlan::SELF_COLLISION : 0u) | (P.friction_dirs ? SubPlan::FRICTION_DIRS : 0u) |
+         (P.limit_speculative ? SubPlan::LIMIT_SPECULATIVE : 0u) | (P.erp_deep != P.erp ? SubPlan::ERP_DEEP : 0u) | (P.limit_erp_deep != P.limit_erp ? SubPlan::LIMIT_ERP_DEEP : 0u);
+  pl.n_iter = P.n_iter;
+  return pl;
+}
 
 // the launch needs the build with the extended contact rows (Pmc::substep_impl<.., XROWS = true>): one of the round-6 switches is off its default
 LL_HD bool pmc_wants_xrows(const StepParams& P) { return P.self_friction > 0.0f || P.pair_friction > 0.0f || P.max_pair != LLM_MAX_PAIR; }

@@ -1071,10 +1071,28 @@ struct Pmc {
   // the launch picks it when one of the three switches is off its default (pmc_wants_xrows).
   template <bool TERRAIN, bool PAIR = false, bool CONE = false, bool XROWS = false>
   static LL_HD void substep_impl(const L& ln, const StepParams& P_in, Base& bs, F* q, F* qd, const F* tgt, int env, int sidx, const SubstepExtra* ex,
-                                 const LinkC* held) {   // held: the own-link constants if the caller keeps them in registers, or null
+                                 const LinkC* held, const SubPlan* plan = nullptr) {   // held: the own-link constants if the caller keeps them in registers, or null; plan: the step's SubPlan (pmc_params.hpp), or null
 #define PMC_TSS(k) do { if (sidx == 5) PMC_TS(k); } while (0)
     PMC_PHASE("sub.kinematics");
     const StepParams& P = (L::kParamsReload > 1) ? ln.params(P_in) : P_in;
+    // what the substep branches on: a bit of the step's plan word where the caller made one, the argument itself otherwise (wave-uniform either way, and the same answer)
+#if PMC_SUB_PLAN
+    const bool planned = plan != nullptr;
+    SubPlan pl;
+    pl.w = planned ? plan->w : 0u; pl.n_iter = planned ? plan->n_iter : 0;
+    if (planned) { PMC_PLAN_FRESH(pl.w); PMC_PLAN_FRESH(pl.n_iter); }
+#define PMC_PLANNED(from_plan, from_args) (planned ? (from_plan) : (from_args))
+#else
+#define PMC_PLANNED(from_plan, from_args) (from_args)
+#endif
+#define SUB_MAX_CONTACTS PMC_PLANNED(pl.max_contacts(), P.max_contacts)
+#define SUB_MAX_SELF PMC_PLANNED(pl.max_self(), P.max_self)
+#define SUB_N_ITER PMC_PLANNED(pl.n_iter, P.n_iter)
+#define SUB_SELF_COLLISION PMC_PLANNED(pl.has(SubPlan::SELF_COLLISION), P.self_collision > 0.5f)
+#define SUB_FRICTION_DIRS PMC_PLANNED(pl.has(SubPlan::FRICTION_DIRS), P.friction_dirs)
+#define SUB_LIMIT_SPECULATIVE PMC_PLANNED(pl.has(SubPlan::LIMIT_SPECULATIVE), P.limit_speculative)
+#define SUB_ERP_DEEP PMC_PLANNED(pl.has(SubPlan::ERP_DEEP), P.erp_deep != P.erp)
+#define SUB_LIMIT_ERP_DEEP PMC_PLANNED(pl.has(SubPlan::LIMIT_ERP_DEEP), P.limit_erp_deep != P.limit_erp)
     const float* legc = P.legc;
     const float* bc = P.basec;
     const float dt = P.dt;
@@ -1363,7 +1381,7 @@ struct Pmc {
     F my_depth = far_, my_sub = zero, my_jj = zero;
     LL_UNROLL
     for (int s = 0; s < PMC_K; s++) {
-      if (s >= P.max_contacts) break;                       // (spec override LLM_SPEC_MAX_CONTACTS_PER_LEG; 4 unless a deviation study says otherwise)
+      if (s >= SUB_MAX_CONTACTS) break;                       // (spec override LLM_SPEC_MAX_CONTACTS_PER_LEG; 4 unless a deviation study says otherwise)
       F m = depth[0];
       for (int jj = 1; jj < NC; jj++) m = lm::min_(m, depth[jj]);
       F mq = L::submin(m);
@@ -1436,12 +1454,12 @@ struct Pmc {
       for (int i = 0; i < 6; i++) nn = nn + lgt[i] * lgt[i];
       // (the second ERP -- Bullet: none beyond 0.04 rad -- under a wave-uniform test of its own: nothing of it is live in the common path of the builds that are short of registers)
       F lerp = ln.lane_f(P.limit_erp * inv_dt);
-      if (P.limit_erp_deep != P.limit_erp) lerp = lm::sel(d > P.erp_deep_below, lerp, ln.lane_f(P.limit_erp_deep * inv_dt));
+      if (SUB_LIMIT_ERP_DEEP) lerp = lm::sel(d > P.erp_deep_below, lerp, ln.lane_f(P.limit_erp_deep * inv_dt));
       rl.c = sg * qsj + lm::sel(d > 0.0f, d * inv_dt, d * lerp);
       // which rows enter the solve.  limit_speculative (rounds 1 - 4): every row that can act within the substep (free approach speed below the gate);
       // otherwise Bullet's rule (btMultiBodyJointLimitConstraint): only a joint that is past its limit has a row -- rare, so most substeps
       // of most waves skip the limit section altogether (any_l below)
-      B lvalid = lm::and_(lm::and_(has, P.limit_speculative ? (rl.c < P.limit_gate) : lm::not_(d > 0.0f)), ln.lane_f(PMC_ABL(2) ? 0.0f : 1.0f) > 0.5f);
+      B lvalid = lm::and_(lm::and_(has, SUB_LIMIT_SPECULATIVE ? (rl.c < P.limit_gate) : lm::not_(d > 0.0f)), ln.lane_f(PMC_ABL(2) ? 0.0f : 1.0f) > 0.5f);
       rl.inv = lm::sel(lvalid, one / nn, zero);
       any_l[0] = L::any(lm::and_(lvalid, ln.is_sub(0))); any_l[1] = L::any(lm::and_(lvalid, ln.is_sub(1)));
       any_l[2] = L::any(lm::and_(lvalid, ln.is_sub(2)));
@@ -1545,14 +1563,14 @@ struct Pmc {
       }
       F depth_c = my_depth;
       F cerp = ln.lane_f(P.erp * inv_dt);
-      if (P.erp_deep != P.erp) cerp = lm::sel(depth_c > P.erp_deep_below, cerp, ln.lane_f(P.erp_deep * inv_dt));       // (LLM_SPEC_ERP_DEEP: not the spec; wave-uniform, see the limit rows)
+      if (SUB_ERP_DEEP) cerp = lm::sel(depth_c > P.erp_deep_below, cerp, ln.lane_f(P.erp_deep * inv_dt));       // (LLM_SPEC_ERP_DEEP: not the spec; wave-uniform, see the limit rows)
       F bias = lm::sel(depth_c > 0.0f, depth_c * inv_dt, lm::max_(depth_c * cerp, ln.lane_f(-P.max_depen)));
       // joint j moves the point iff the point's link is at or below joint j: link >= j+1
       F on1 = lm::sel(link > 0.5f, one, zero), on2 = lm::sel(link > 1.5f, one, zero), on3 = lm::sel(link > 2.5f, one, zero);
       V3l rr1 = Pb - k.p1, rr2 = Pb - k.p2, rr3 = Pb - k.p3;
       V3l a1v = mk3<F>(one, zero, zero);
       V3l d1 = scale(cross(a1v, rr1), on1), d2 = scale(cross(k.a2, rr2), on2), d3 = scale(cross(k.a2, rr3), on3);
-      if (P.friction_dirs) {
+      if (SUB_FRICTION_DIRS) {
         // LLM_SPEC_FRICTION_DIRS = 1 (deviation study; Bullet's default direction rule as published in convertMultiBodyContact): the first
         // friction direction runs along the lateral velocity of the contact point after the unconstrained update, the second is t1 x n;
         // a point that does not slide keeps btPlaneSpace1(n)
@@ -1602,7 +1620,7 @@ struct Pmc {
     if (self_fric) { self_row_clear(ln, sf[0][0]); self_row_clear(ln, sf[0][1]); self_row_clear(ln, sf[1][0]); self_row_clear(ln, sf[1][1]); }
     bool any_self = false;
     int n_self_w = 0;                   // self-collision slots in use by some env of the wave
-    if (P.self_collision > 0.5f && !PMC_ABL(512)) {                                 // (ablation 512: no self-collision at all)
+    if (SUB_SELF_COLLISION && !PMC_ABL(512)) {                                 // (ablation 512: no self-collision at all)
       V3l TA = k.p2 + mul(k.R2, ld3c(ln, legc, LC_CAPS)), TB = k.p2 + mul(k.R2, ld3c(ln, legc, LC_CAPS + 3));
       V3l SA = k.p3 + mul(k.R3, ld3c(ln, legc, LC_CAPS + 6)), SB = k.p3 + mul(k.R3, ld3c(ln, legc, LC_CAPS + 9));
       F rT = ln.legc(legc, LC_CAPS + 12), rS = ln.legc(legc, LC_CAPS + 13);
@@ -1648,12 +1666,12 @@ struct Pmc {
         if (pass == 1) valid = lm::and_(valid, legf < 1.5f);                    // pairs {0,2} and {1,3}, once each
         cd[pass] = lm::sel(valid, dep, far_);
       }
-      any_self = L::any(lm::min_(cd[0], cd[1]) < 1.0e29f) && !PMC_ABL(256) && P.max_self > 0;          // (ablation 256: detection only)
+      any_self = L::any(lm::min_(cd[0], cd[1]) < 1.0e29f) && !PMC_ABL(256) && SUB_MAX_SELF > 0;          // (ablation 256: detection only)
       if (any_self) {
         PMC_PHASE("sub.self_rows");
         LL_UNROLL
         for (int slot = 0; slot < 2; slot++) {
-          if (slot >= P.max_self) break;                                             // (spec override LLM_SPEC_MAX_SELF)
+          if (slot >= SUB_MAX_SELF) break;                                             // (spec override LLM_SPEC_MAX_SELF)
           if (slot == 1 && !L::any(lm::min_(cd[0], cd[1]) < 1.0e29f)) break;        // nobody in the wave has a second one
           n_self_w = slot + 1;
           F dlane = lm::min_(cd[0], cd[1]);
@@ -1895,7 +1913,7 @@ struct Pmc {
     auto pgs_loop = [&](auto lim_k, auto con_k, auto self_k) __attribute__((always_inline)) {
       constexpr int LIM_K = decltype(lim_k)::value, CON_K = decltype(con_k)::value, SELF_K = decltype(self_k)::value;
       LL_NOUNROLL
-      for (int it = 0; it < P.n_iter; it++) {
+      for (int it = 0; it < SUB_N_ITER; it++) {
         PMC_PHASE("pgs.limit_round");
         if (LIM_K > 0 || (LIM_K < 0 && any_limit)) gs_round<true, true>(ln, rl, big, VA, VB, VJ);
         PMC_PHASE("pgs.normal_round");
@@ -1982,6 +2000,15 @@ struct Pmc {
       q[j] = q[j] + qs[j] * dt;
     }
   }
+#undef PMC_PLANNED
+#undef SUB_MAX_CONTACTS
+#undef SUB_MAX_SELF
+#undef SUB_N_ITER
+#undef SUB_SELF_COLLISION
+#undef SUB_FRICTION_DIRS
+#undef SUB_LIMIT_SPECULATIVE
+#undef SUB_ERP_DEEP
+#undef SUB_LIMIT_ERP_DEEP
 
   // ---------------------------------------------------------------------------------------------------
   // mocap reference (ML:65-166)
@@ -2267,6 +2294,9 @@ struct Pmc {
   // act_in: the env's actions, one register per joint of the lane's leg (read from P.actions or drawn by the caller)
   // OBST (set_obstacle builds): the jump obstacle of the episode is a static box the robot collides with during the substeps
   // sl: index of this control step inside its launch (ll_step_random_n runs n_steps of them back to back; 0 otherwise)
+  // does the lane policy take the substep plan?  (lanes.hpp WithSubPlan; a policy that does not say -- the host build's -- takes it)
+  template <class T, class = void> struct wants_sub_plan { static constexpr bool value = true; };
+  template <class T> struct wants_sub_plan<T, std::void_t<decltype(T::kSubPlan)>> { static constexpr bool value = T::kSubPlan; };
   template <bool OBST = false, bool CONE = false, bool XROWS = false>
   static LL_HD void step_env(const L& ln, const StepParams& P_in, int env, const F* act_in, int sl = 0) {
     const StepParams& P = ln.params(P_in);
@@ -2309,9 +2339,15 @@ struct Pmc {
     const LinkC* held = nullptr;
     if (L::kHoldLink) { lkh = own_link_held(ln, P.legc); held = &lkh; }
     PMC_PHASE("step.substep_loop");
+#if PMC_SUB_PLAN
+    const SubPlan pl = pmc_sub_plan(P);                                      // once per control step, from the argument block as this step reads it
+    const SubPlan* plan = (L::kParamsReload < 2 && wants_sub_plan<L>::value) ? &pl : nullptr;
+#else
+    const SubPlan* plan = nullptr;
+#endif
     for (int s = 0; s < P.n_sub; s++) {                                      // PLE:202
-      if (OBST) substep_impl<true, false, CONE, XROWS>(ln, P, bs, q, qd, tgt, env, s, &ex, held);
-      else substep_impl<false, false, CONE, XROWS>(ln, P, bs, q, qd, tgt, env, s, nullptr, held);   // PLE:204-206
+      if (OBST) substep_impl<true, false, CONE, XROWS>(ln, P, bs, q, qd, tgt, env, s, &ex, held, plan);
+      else substep_impl<false, false, CONE, XROWS>(ln, P, bs, q, qd, tgt, env, s, nullptr, held, plan);   // PLE:204-206
       t_loc = t;                                                             // PLE:208 motion.step(time BEFORE the increment), quirk Q2
       t += P.dt_d;                                                           // PLE:210
     PMC_TS(10 + (s < 20 ? s : 20));

@@ -58,12 +58,20 @@ typedef float f16 __attribute__((ext_vector_type(16)));
 #define PL16(i) "v_permlane16_swap_b32 %" #i ", %16\n"
 #define PL32(i) "v_permlane32_swap_b32 %" #i ", %16\n"
 #define PKFMA(i) "v_pk_fma_f32 %" #i ", %" #i ", %16, %17\n"
+// scalar argument fetches and lane reads feeding a wave-uniform branch (%21 = SGPR pair: the kernarg segment, whose first line is warm in the constant cache)
+#define SLD_WAIT(i) "s_load_dword s40, %21, 0x0\ns_waitcnt lgkmcnt(0)\n"
+#define SLD_FMA4_WAIT(i) "s_load_dword s40, %21, 0x0\n" FMA64(0) FMA64(1) FMA64(2) FMA64(3) "s_waitcnt lgkmcnt(0)\n"
+#define SLD_FMA16_WAIT(i) "s_load_dword s40, %21, 0x0\n" R4(FMA64, 0, 1, 2, 3) R4(FMA64, 4, 5, 6, 7) R4(FMA64, 8, 9, 10, 11) R4(FMA64, 12, 13, 14, 15) "s_waitcnt lgkmcnt(0)\n"
+#define SLD_BR(i) "s_load_dword s40, %21, 0x0\ns_waitcnt lgkmcnt(0)\ns_cmp_eq_u32 s40, 0x7fffffff\ns_cbranch_scc1 1f\n1:\n"
+#define SCMP_BR(i) "s_cmp_eq_u32 s41, 0x7fffffff\ns_cbranch_scc1 1f\n1:\n"
+#define BIT_BR(i) "s_bitcmp1_b32 s41, 31\ns_cbranch_scc1 1f\n1:\n"
+#define RDL_BR(i) "v_readlane_b32 s40, %" #i ", 3\ns_cmp_eq_u32 s40, 0x7fffffff\ns_cbranch_scc1 1f\n1:\n"
 
 enum {
   K_ADD32, K_MUL32, K_FMAC32, K_FMA64, K_MUL64, K_FMAK, K_FMAS, K_ADDLIT, K_MOV32, K_CND64, K_MED3, K_FMACDPP, K_MOVDPP, K_LSHL, K_RSQ, K_ACCW, K_ACCR,
   K_SNOP, K_SNOP1, K_SMOV, K_SADD, K_FMA_SNOP, K_FMA_SMOV, K_MUL_SMOV, K_MUL_SNOP, K_FMA_ACCR, K_READLANE, K_DSR, K_DSR_FMA, K_PL16, K_PL32, K_PKFMA,
   K_MFMA16_DEP, K_MFMA16_IND, K_MFMA4_DEP, K_MFMA4_IND, K_MFMA16x6_ALONE, K_MFMA16x6_I4, K_MFMA16x6_I6, K_MFMA16x6_I8, K_V36_ALONE, K_MFMA16x6_V16, K_MFMA16x6_V32, K_MFMA16x6_V48, K_V48_ALONE, K_MFMA16x6_READ, K_MFMA4x3_READ,
-  K_TURN, K_CONE, K_COUNT
+  K_TURN, K_CONE, K_SLD_WAIT, K_SLD_FMA4_WAIT, K_SLD_FMA16_WAIT, K_SLD_BR, K_SCMP_BR, K_BIT_BR, K_RDL_BR, K_COUNT
 };
 struct Info { const char* name; int n; };
 static const Info INFO[K_COUNT] = {
@@ -80,7 +88,10 @@ static const Info INFO[K_COUNT] = {
   {"36 independent v_fma alone", 36}, {"chain of 6 MFMA 16x16x1_4b + 16 independent v_fma", 22}, {"chain of 6 MFMA 16x16x1_4b + 32 independent v_fma", 38},
   {"chain of 6 MFMA 16x16x1_4b + 48 independent v_fma", 54}, {"48 independent v_fma alone", 48}, {"chain of 6 MFMA 16x16x1_4b, then a VALU read of the result", 7},
   {"chain of 3 MFMA 4x4x1_16b, then a VALU read of the result", 4},
-  {"solver turn x16: v_med3, v_cndmask_e64, s_nop 0, v_fmac_dpp", 64}, {"cone turn x4 (12 slots each, pipelined form)", 49}};
+  {"solver turn x16: v_med3, v_cndmask_e64, s_nop 0, v_fmac_dpp", 64}, {"cone turn x4 (12 slots each, pipelined form)", 49},
+  {"s_load_dword (warm line) + s_waitcnt lgkmcnt(0) (pairs)", 32}, {"s_load_dword + 4 v_fma + s_waitcnt lgkmcnt(0)", 96}, {"s_load_dword + 16 v_fma + s_waitcnt lgkmcnt(0)", 288},
+  {"s_load_dword + s_waitcnt + s_cmp + s_cbranch not taken", 64}, {"s_cmp + s_cbranch not taken (SGPR held)", 32}, {"s_bitcmp1 + s_cbranch not taken (SGPR held)", 32},
+  {"v_readlane_b32 + s_cmp + s_cbranch not taken", 48}};
 
 struct WaveRec { uint64_t cycles; };
 
@@ -99,10 +110,11 @@ __global__ __launch_bounds__(256) void probe(WaveRec* out, int iters, float b, f
   unsigned long long mask = 0x0001000100010001ull << (iters & 3);
   float sc = c;
   unsigned ldsa = (threadIdx.x & 63) * 4;
-  asm volatile("" : "+s"(mask), "+s"(sc));
+  const __attribute__((address_space(4))) void* karg = (const __attribute__((address_space(4))) void*)__builtin_amdgcn_kernarg_segment_ptr();
+  asm volatile("" : "+s"(mask), "+s"(sc), "+s"(karg));
   asm volatile("s_memtime %0\ns_waitcnt lgkmcnt(0)" : "=s"(t0));
   for (int it = 0; it < iters; it++) {
-#define BODY(S) asm volatile(S : OPS16 : "v"(b), "v"(c), "s"(mask), "s"(sc), "v"(ldsa) : "scc", "s40", "s41", "a0", "a1", "a2", "a3", "a4", "a5", "a6", "a7", "a8", "a9", "a10", "a11", "a12", "a13", "a14", "a15")
+#define BODY(S) asm volatile(S : OPS16 : "v"(b), "v"(c), "s"(mask), "s"(sc), "v"(ldsa), "s"(karg) : "scc", "s40", "s41", "a0", "a1", "a2", "a3", "a4", "a5", "a6", "a7", "a8", "a9", "a10", "a11", "a12", "a13", "a14", "a15")
     if constexpr (KIND == K_ADD32) BODY(R64(ADD32));
     if constexpr (KIND == K_MUL32) BODY(R64(MUL32));
     if constexpr (KIND == K_FMAC32) BODY(R64(FMAC32));
@@ -190,6 +202,13 @@ __global__ __launch_bounds__(256) void probe(WaveRec* out, int iters, float b, f
               "v_fmac_f32_dpp %0, %6, %12 row_newbcast:" #L " row_mask:0xf bank_mask:0xf\nv_fmac_f32_dpp %1, %6, %13 row_newbcast:" #L " row_mask:0xf bank_mask:0xf\n"
       BODY(CT(0) CT(4) CT(8) CT(12) "v_cndmask_b32_e64 %3, %3, %6, %18\n");
     }
+    if constexpr (KIND == K_SLD_WAIT) BODY(R16(SLD_WAIT));
+    if constexpr (KIND == K_SLD_FMA4_WAIT) BODY(R16(SLD_FMA4_WAIT));
+    if constexpr (KIND == K_SLD_FMA16_WAIT) BODY(R16(SLD_FMA16_WAIT));
+    if constexpr (KIND == K_SLD_BR) BODY(R16(SLD_BR));
+    if constexpr (KIND == K_SCMP_BR) BODY(R16(SCMP_BR));
+    if constexpr (KIND == K_BIT_BR) BODY(R16(BIT_BR));
+    if constexpr (KIND == K_RDL_BR) BODY(R16(RDL_BR));
   }
   asm volatile("s_memtime %0\ns_waitcnt lgkmcnt(0)" : "=s"(t1));
   float s = 0;
