@@ -237,7 +237,8 @@ struct GpuLanes {
     "v_add_f32_dpp %5, %5, %5 " CTRL " row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t"
   static LL_D void rsum6(const F* x, float* out) {
     float q0 = x[0], q1 = x[1], q2 = x[2], q3 = x[3], q4 = x[4], q5 = x[5];
-    asm("s_nop 1\n\t" LL_STEP6("quad_perm:[1,0,3,2]") LL_STEP6("quad_perm:[2,3,0,1]") LL_STEP6("row_ror:4") LL_STEP6("row_ror:8") "s_nop 0"
+    // (row_ror:8 before row_ror:4, as qsum: every lane adds (q0 + q2) + (q1 + q3) over the legs, so the sum is the same float in all 16 lanes)
+    asm("s_nop 1\n\t" LL_STEP6("quad_perm:[1,0,3,2]") LL_STEP6("quad_perm:[2,3,0,1]") LL_STEP6("row_ror:8") LL_STEP6("row_ror:4") "s_nop 0"
         : "+v"(q0), "+v"(q1), "+v"(q2), "+v"(q3), "+v"(q4), "+v"(q5));
     out[0] = q0; out[1] = q1; out[2] = q2; out[3] = q3; out[4] = q4; out[5] = q5;
   }
@@ -361,24 +362,44 @@ struct GpuLanes {
   // group (8 v_permlane32_swap + 8 v_permlane16_swap, gfx950) brings them home, register index = column index.  6 MFMA + 16 swaps instead of 96 half-rate
   // v_fmac_f32_dpp (gram4 x 4); exact float32 (tools/mfma_gram_probe.hip: bit-identical to the shuffle statement on MI355X).  MFMA ignores EXEC; the swaps fetch from lanes outside
   // EXEC too (fi = 1: a wave whose last rows hold no env still owns the registers the matrix core wrote there -- with fi = 0 the first version read zeros and failed every test with a
-  // partial wave).  EXPERIMENT, off by default (LL_MFMA_GRAM above): the fi = 1 form has not been through the GPU suite.
+  // partial wave; fi = 1 alone did not mend that, see PARTIAL WAVES below).  EXPERIMENT, off by default (LL_MFMA_GRAM above).
   static constexpr bool kGram16 = LL_MFMA_GRAM != 0;
   typedef float ll_f16v __attribute__((ext_vector_type(16)));
+  // PARTIAL WAVES (tests/test_gpu_lane_prims.py): entry D_b[i][j] of row b is produced in the registers of lane 16 (i / 4) + j -- for i >= 4 in ANOTHER row of the wave, which in a
+  // tail wave may sit the step out.  The matrix core writes those lanes whatever EXEC says, but every copy out of the accumulator (v_accvgpr_read) and every swap is a
+  // VALU instruction that skips them: left to the compiler, the swaps fetched stale registers from the idle rows and g[4 ..] of the active rows came back 0.  So the
+  // chain, the copies out of a[0:15] and the block transpose are ONE asm statement that runs under a full EXEC (restored at its end); what the idle rows' lanes hold in
+  // x and y only reaches the idle rows' own blocks.
+#define LL_SW32(A, B) "v_permlane32_swap_b32_e64 %" #A ", %" #B " fi:1\n\t"
+#define LL_SW16(A, B) "v_permlane16_swap_b32_e64 %" #A ", %" #B " fi:1\n\t"
+#define LL_GRAM_TRANSPOSE                                                                                                              \
+    LL_SW32(0, 8) LL_SW32(4, 12) LL_SW32(1, 9) LL_SW32(5, 13) LL_SW32(2, 10) LL_SW32(6, 14) LL_SW32(3, 11) LL_SW32(7, 15)              \
+    LL_SW16(0, 4) LL_SW16(8, 12) LL_SW16(1, 5) LL_SW16(9, 13) LL_SW16(2, 6) LL_SW16(10, 14) LL_SW16(3, 7) LL_SW16(11, 15)
+#define LL_ACC_RD(D_, A_) "v_accvgpr_read_b32 %" #D_ ", a" #A_ "\n\t"
   static LL_D void gram16(const F* x, const F* y, F* g) {
-    ll_f16v acc;
-    for (int i = 0; i < 16; i++) acc[i] = 0.0f;
-    for (int i = 0; i < 6; i++) acc = __builtin_amdgcn_mfma_f32_16x16x1f32(x[i], y[i], acc, 0, 0, 0);
-    unsigned R[16];
-    for (int i = 0; i < 16; i++) R[i] = __float_as_uint(acc[i]);
-    for (int r = 0; r < 4; r++) {
-      const auto a = __builtin_amdgcn_permlane32_swap(R[r], R[8 + r], true, false); R[r] = a[0]; R[8 + r] = a[1];
-      const auto b = __builtin_amdgcn_permlane32_swap(R[4 + r], R[12 + r], true, false); R[4 + r] = b[0]; R[12 + r] = b[1];
-    }
-    for (int r = 0; r < 4; r++) {
-      const auto a = __builtin_amdgcn_permlane16_swap(R[r], R[4 + r], true, false); R[r] = a[0]; R[4 + r] = a[1];
-      const auto b = __builtin_amdgcn_permlane16_swap(R[8 + r], R[12 + r], true, false); R[8 + r] = b[0]; R[12 + r] = b[1];
-    }
-    for (int i = 0; i < 16; i++) g[i] = __uint_as_float(R[i]);
+    float r0, r1, r2, r3, r4, r5, r6, r7, r8, r9, r10, r11, r12, r13, r14, r15;
+    unsigned long long sv;
+    asm volatile("s_mov_b64 %16, exec\n\t"
+                 "s_mov_b64 exec, -1\n\t"
+                 "v_mfma_f32_16x16x1_4b_f32 a[0:15], %17, %23, 0\n\t"
+                 "v_mfma_f32_16x16x1_4b_f32 a[0:15], %18, %24, a[0:15]\n\t"
+                 "v_mfma_f32_16x16x1_4b_f32 a[0:15], %19, %25, a[0:15]\n\t"
+                 "v_mfma_f32_16x16x1_4b_f32 a[0:15], %20, %26, a[0:15]\n\t"
+                 "v_mfma_f32_16x16x1_4b_f32 a[0:15], %21, %27, a[0:15]\n\t"
+                 "v_mfma_f32_16x16x1_4b_f32 a[0:15], %22, %28, a[0:15]\n\t"
+                 "s_nop 15\n\t"            // the result of an 8-pass MFMA into a VALU read
+                 LL_ACC_RD(0, 0) LL_ACC_RD(1, 1) LL_ACC_RD(2, 2) LL_ACC_RD(3, 3) LL_ACC_RD(4, 4) LL_ACC_RD(5, 5) LL_ACC_RD(6, 6) LL_ACC_RD(7, 7)
+                 LL_ACC_RD(8, 8) LL_ACC_RD(9, 9) LL_ACC_RD(10, 10) LL_ACC_RD(11, 11) LL_ACC_RD(12, 12) LL_ACC_RD(13, 13) LL_ACC_RD(14, 14) LL_ACC_RD(15, 15)
+                 "s_nop 1\n\t"
+                 LL_GRAM_TRANSPOSE
+                 "s_mov_b64 exec, %16\n\t"
+                 "s_nop 4"
+                 : "=&v"(r0), "=&v"(r1), "=&v"(r2), "=&v"(r3), "=&v"(r4), "=&v"(r5), "=&v"(r6), "=&v"(r7), "=&v"(r8), "=&v"(r9), "=&v"(r10), "=&v"(r11), "=&v"(r12),
+                   "=&v"(r13), "=&v"(r14), "=&v"(r15), "=&s"(sv)
+                 : "v"(x[0]), "v"(x[1]), "v"(x[2]), "v"(x[3]), "v"(x[4]), "v"(x[5]), "v"(y[0]), "v"(y[1]), "v"(y[2]), "v"(y[3]), "v"(y[4]), "v"(y[5])
+                 : "a0", "a1", "a2", "a3", "a4", "a5", "a6", "a7", "a8", "a9", "a10", "a11", "a12", "a13", "a14", "a15");
+    g[0] = r0; g[1] = r1; g[2] = r2; g[3] = r3; g[4] = r4; g[5] = r5; g[6] = r6; g[7] = r7;
+    g[8] = r8; g[9] = r9; g[10] = r10; g[11] = r11; g[12] = r12; g[13] = r13; g[14] = r14; g[15] = r15;
   }
   // ---- the Gram blocks as a BACKGROUND job of the matrix cores (round 6; WithGramPipe below) -------------------------------------------------------------------
   // Round 5's gram16 issued its six dependent MFMAs back to back and read the result at once: a wave issues in order, so it stood still for the whole chain
@@ -401,19 +422,42 @@ struct GpuLanes {
     __builtin_amdgcn_sched_barrier(0);
   }
   // g[L] = sum_k y[k] * (x[k] of lane L of my row): the finished accumulator's 4 x 4 block transpose between register block and row group (see gram16)
+  // (partial waves, as gram16: the copies out of the accumulator and the swaps run under a full EXEC.  The accumulator is asked for in accumulation registers, where the
+  //  chain of gram_mfma left it, so that no compiler-made copy -- which would skip the idle rows' lanes -- stands between the matrix core and these reads.
+  //  LIMIT: that is a request, not a guarantee.  gram_mfma is a builtin under the caller's EXEC: its zero start reaches the idle rows' lanes only as the inline constant the
+  //  compiler folds it into, and whatever the compiler moves between the chain and these reads (v_accvgpr_write / read, a VGPR-form MFMA) skips those lanes again.  The
+  //  single-wave test proves the partial wave for ITS code generation only; a kernel that turns kGramPipe on has to be held to gram4 under a partial wave itself)
   static LL_D void gram_collect(const GramAcc& a, F* g) {
-    unsigned R[16];
-    for (int i = 0; i < 16; i++) R[i] = __float_as_uint(a.v[i]);
-    for (int r = 0; r < 4; r++) {
-      const auto p = __builtin_amdgcn_permlane32_swap(R[r], R[8 + r], true, false); R[r] = p[0]; R[8 + r] = p[1];
-      const auto q = __builtin_amdgcn_permlane32_swap(R[4 + r], R[12 + r], true, false); R[4 + r] = q[0]; R[12 + r] = q[1];
-    }
-    for (int r = 0; r < 4; r++) {
-      const auto p = __builtin_amdgcn_permlane16_swap(R[r], R[4 + r], true, false); R[r] = p[0]; R[4 + r] = p[1];
-      const auto q = __builtin_amdgcn_permlane16_swap(R[8 + r], R[12 + r], true, false); R[8 + r] = q[0]; R[12 + r] = q[1];
-    }
-    for (int i = 0; i < 16; i++) g[i] = __uint_as_float(R[i]);
+    float r0, r1, r2, r3, r4, r5, r6, r7, r8, r9, r10, r11, r12, r13, r14, r15;
+    unsigned long long sv;
+#define LL_ACC_RD8                                                                                                                        \
+    "s_mov_b64 %8, exec\n\t"                                                                                                             \
+    "s_mov_b64 exec, -1\n\t"                                                                                                             \
+    "s_nop 15\n\t"                                                                                                                       \
+    "v_accvgpr_read_b32 %0, %9\n\tv_accvgpr_read_b32 %1, %10\n\tv_accvgpr_read_b32 %2, %11\n\tv_accvgpr_read_b32 %3, %12\n\t"            \
+    "v_accvgpr_read_b32 %4, %13\n\tv_accvgpr_read_b32 %5, %14\n\tv_accvgpr_read_b32 %6, %15\n\tv_accvgpr_read_b32 %7, %16\n\t"          \
+    "s_mov_b64 exec, %8\n\t"                                                                                                             \
+    "s_nop 4"
+    asm volatile(LL_ACC_RD8 : "=&v"(r0), "=&v"(r1), "=&v"(r2), "=&v"(r3), "=&v"(r4), "=&v"(r5), "=&v"(r6), "=&v"(r7), "=&s"(sv)
+                 : "a"(a.v[0]), "a"(a.v[1]), "a"(a.v[2]), "a"(a.v[3]), "a"(a.v[4]), "a"(a.v[5]), "a"(a.v[6]), "a"(a.v[7]));
+    asm volatile(LL_ACC_RD8 : "=&v"(r8), "=&v"(r9), "=&v"(r10), "=&v"(r11), "=&v"(r12), "=&v"(r13), "=&v"(r14), "=&v"(r15), "=&s"(sv)
+                 : "a"(a.v[8]), "a"(a.v[9]), "a"(a.v[10]), "a"(a.v[11]), "a"(a.v[12]), "a"(a.v[13]), "a"(a.v[14]), "a"(a.v[15]));
+#undef LL_ACC_RD8
+    asm volatile("s_mov_b64 %16, exec\n\t"
+                 "s_mov_b64 exec, -1\n\t"
+                 "s_nop 1\n\t"
+                 LL_GRAM_TRANSPOSE
+                 "s_mov_b64 exec, %16\n\t"
+                 "s_nop 4"
+                 : "+v"(r0), "+v"(r1), "+v"(r2), "+v"(r3), "+v"(r4), "+v"(r5), "+v"(r6), "+v"(r7), "+v"(r8), "+v"(r9), "+v"(r10), "+v"(r11), "+v"(r12), "+v"(r13),
+                   "+v"(r14), "+v"(r15), "=&s"(sv));
+    g[0] = r0; g[1] = r1; g[2] = r2; g[3] = r3; g[4] = r4; g[5] = r5; g[6] = r6; g[7] = r7;
+    g[8] = r8; g[9] = r9; g[10] = r10; g[11] = r11; g[12] = r12; g[13] = r13; g[14] = r14; g[15] = r15;
   }
+#undef LL_ACC_RD
+#undef LL_GRAM_TRANSPOSE
+#undef LL_SW16
+#undef LL_SW32
   // Four Gauss-Seidel turns (lanes S, 4+S, 8+S, 12+S) as one block: v_med3 (clamp the pending increment), v_cndmask (the lane
   // whose turn it is keeps its increment; masks m0..m3 are the lane masks of the four turns), one wait state, v_fmac with a
   // DPP row broadcast (every lane's pending increment moves by nk * d).  4 issue slots per turn.

@@ -139,7 +139,11 @@ struct HostLanes {
   B is_sub(int k) const { bN r; for (int i = 0; i < EW; i++) r.v[i] = ((i & 3) == k); return r; }
   B is_lane(int L) const { bN r; for (int i = 0; i < EW; i++) r.v[i] = (i == L); return r; }
   F lane_f(float x) const { return fN(x); }
-  // sums follow the association of the DPP trees in lanes.hpp
+  // How close this twin is to GpuLanes, one primitive at a time, is recorded in the class table of tests/lane_prims_common.py and held by tests/test_gpu_lane_prims.py:
+  //   * moves (broadcasts, gathers, selects, mins, loads / stores) and the plain sums below are the GPU's bit for bit: qsum, subsum, rsum6, qsum6, subsum3 and sufsum*
+  //     follow the association of the DPP trees in lanes.hpp, and an add rounds once on both sides;
+  //   * whatever multiplies and adds (fmac_rbcast, gram*, turns*, cone_turns4, vel_*) is the GPU's only to rounding: every multiply-add here is a product and a sum
+  //     (-ffp-contract=off), the GPU's v_fmac / v_fma / MFMA round once.  On inputs whose products and sums are exact the two agree bit for bit.
   static float qsum(const F& x) { return (x.v[0] + x.v[8]) + (x.v[4] + x.v[12]); }                 // over legs, leg-uniform input
   static F subsum(const F& x) { fN r; for (int q = 0; q < 4; q++) { float s = (x.v[4 * q] + x.v[4 * q + 1]) + (x.v[4 * q + 2] + x.v[4 * q + 3]); for (int k = 0; k < 4; k++) r.v[4 * q + k] = s; } return r; }
   static F submin(const F& x) { fN r; for (int q = 0; q < 4; q++) { float s = fminf(fminf(x.v[4 * q], x.v[4 * q + 1]), fminf(x.v[4 * q + 2], x.v[4 * q + 3])); for (int k = 0; k < 4; k++) r.v[4 * q + k] = s; } return r; }
@@ -169,13 +173,13 @@ struct HostLanes {
   template <int L_> static void fmac_rbcast_settled(F& acc, const F& x, const F& k) { fmac_rbcast<L_>(acc, x, k); }
   static F settle(const F& x) { return x; }
   static constexpr bool kGram16 = false;       // (as the shipped GPU build: lanes.hpp LL_MFMA_GRAM)
-  static void gram16(const F* x, const F* y, F* g) {     // lanes.hpp GpuLanes::gram16: g[L] = sum_i y[i] * (x[i] of lane L), in the order the MFMA chain accumulates (i = 0 .. 5)
+  static void gram16(const F* x, const F* y, F* g) {     // lanes.hpp GpuLanes::gram16: g[L] = sum_i y[i] * (x[i] of lane L), in the order the MFMA chain accumulates (i = 0 .. 5) but with product and sum rounded separately
     for (int L_ = 0; L_ < EW; L_++) {
       for (int l = 0; l < EW; l++) g[L_].v[l] = 0.0f;
       for (int i = 0; i < 6; i++) for (int l = 0; l < EW; l++) g[L_].v[l] = g[L_].v[l] + x[i].v[L_] * y[i].v[l];
     }
   }
-  // lanes.hpp GpuLanes::gram_mfma / gram_collect (WithGramPipe): the same sums, one k at a time, in the order the MFMA chain accumulates
+  // lanes.hpp GpuLanes::gram_mfma / gram_collect (WithGramPipe): the same sums, one k at a time, in the order the MFMA chain accumulates (unfused, as gram16 above)
   static constexpr bool kGramPipe = false;           // (emul.cpp runs the piped variant under LL_EMUL_GRAM_PIPE)
   struct GramAcc { fN g[EW]; };
   template <int K_> static void gram_mfma(GramAcc& a, const F& x, const F& y) {
@@ -190,7 +194,8 @@ struct HostLanes {
   }
   template <int S_, bool NEG_LO = false> static void turns4(F& u, F& dl, const F& lo_in, const F& hi, const F& k0, const F& k1, const F& k2, const F& k3) {
     const F* ks[4] = {&k0, &k1, &k2, &k3};
-    const fN lo = NEG_LO ? fN(0.0f) - lo_in : lo_in;
+    fN lo = lo_in;
+    if (NEG_LO) for (int l = 0; l < EW; l++) lo.v[l] = -lo_in.v[l];      // the negation the GPU takes (lo = 0 gives -0, and med3 hands that sign on), not 0 - lo
     for (int t = 0; t < 4; t++) {
       const int L_ = 4 * t + S_;
       fN d = lm::med3_(u, lo, hi);
@@ -199,7 +204,8 @@ struct HostLanes {
     }
   }
   template <int H_, bool NEG_LO = false> static void turns8(F& u, F& dl, const F& lo_in, const F& hi, const F* nk) {
-    const fN lo = NEG_LO ? fN(0.0f) - lo_in : lo_in;
+    fN lo = lo_in;
+    if (NEG_LO) for (int l = 0; l < EW; l++) lo.v[l] = -lo_in.v[l];      // the negation the GPU takes (lo = 0 gives -0, and med3 hands that sign on), not 0 - lo
     const int order[2][8] = {{0, 4, 8, 12, 1, 5, 9, 13}, {2, 6, 10, 14, 3, 7, 11, 15}};
     for (int t = 0; t < 8; t++) {
       const int L_ = order[H_][t];
@@ -244,6 +250,7 @@ struct HostLanes {
     }
     return w;
   }
+  // (the sixteen products of a value are summed in LANE ORDER here; the GPU reduces them in a quad-exchange tree followed by row_ror 4 and 8 -- another association: equal to rounding only)
   static void vel_commit(const F& dl, F& lam, const F2& ca01, const F2& ca23, const F2& cb01, const F2& cj01, const F2& cj23, F& VA, F& VB, F& VJ) {
     const fN* ca[4] = {&ca01.x, &ca01.y, &ca23.x, &ca23.y};
     const fN* cb[2] = {&cb01.x, &cb01.y};
