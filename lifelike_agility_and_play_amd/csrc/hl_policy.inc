@@ -182,8 +182,8 @@ __device__ __forceinline__ void hl_load_state(const float* __restrict__ state, i
 
 // tpolicies lstm_embed_block, one step (oracle/epmc_policy.py): x [256][16] k-major in `x`; weights k0 .. k0+8 = wx, wh, b, beta_x, gamma_x,
 // beta_h, gamma_h, beta_c, gamma_c.  zbuf: 256 x 16 floats of scratch.  Leaves c', h' in cs, hs and in the state buffer; returns h'_j of
-// this lane's (row, unit).  Starts and ends at a barrier.
-template <class WT, class RM>
+// this lane's (row, unit).  Starts and ends at a barrier.  ONCHIP (the scorer, hl_score.inc): c', h' stay in cs, hs alone and `state` is not touched.
+template <bool ONCHIP = false, class WT, class RM>
 __device__ __forceinline__ float hl_lstm(const WT& W, int k0, const float* x, float* zbuf, float* cs, float* hs, float* __restrict__ state, int sdim, int off,
                                          const RM& R, int wave, int lane, int tid) {
   pol_dense(x, 256, W.a[k0], W.zero, 128, zbuf, 0, wave, lane);                     // x Wx   rows 0..127
@@ -210,7 +210,9 @@ __device__ __forceinline__ float hl_lstm(const WT& W, int k0, const float* x, fl
   const float h = hl_sigmoid(z[2]) * tanhf((c - mc) * rc * W.a[k0 + 8][j] + W.a[k0 + 7][j]);
   cs[j * POL_M + m] = c;
   hs[j * POL_M + m] = h;
-  if (R.live(m)) { state[(long)r * sdim + off + j] = c; state[(long)r * sdim + off + 32 + j] = h; }
+  if constexpr (!ONCHIP) {
+    if (R.live(m)) { state[(long)r * sdim + off + j] = c; state[(long)r * sdim + off + 32 + j] = h; }
+  }
   __syncthreads();
   return h;
 }
@@ -249,6 +251,16 @@ struct HlPg {
   float *pm, *ps;      // [16][16]: per-part max and sum of exp of the z logits
 };
 
+// what the scoring launch (hl_score.inc) hands the policy chain in place of draws: the recorded heads of one time step and where their neglogp and
+// entropy go.  Row r's A field ([heading (SEPMC)] | z code | action[12]) is a + r * astride, its output row (LLS_OUT_FLOATS columns: neglogp[nh] |
+// entropy[nh] | ..) out + r * ostride.  hcs, hhs: LDS [32][16], SEPMC's high-level LSTM state (the mid level's own lives in HlLds::cs, hs).
+struct HlFed {
+  const float* a;
+  float* out;
+  long astride, ostride;
+  float *hcs, *hhs;
+};
+
 struct HlLds {
   float big[2 * 256 * POL_M];   // two activation buffers b0 | b1; the percept stacks' intermediate maps while those run
   float xs[136 * POL_M];        // normalised prop (135)
@@ -263,12 +275,17 @@ struct HlLds {
 // The mid level (EPMC's whole policy; SEPMC's mlc_encoder and llc) with the EPMC checkpoint's array numbers; the SEPMC arrays are OFF = 50
 // further on.  On entry: xs, and the target [3][16] in L.vin.  Writes actions / code of the map's rows.
 // PG: the PPO actor's heads (HlPg): the code and the action sampled when g.sample, neglogp of both when g.neglogp.
-template <int OFF, bool PG = false, class WT, class RM>
+// FED (with PG; the scorer, hl_score.inc): nothing is chosen or drawn.  The z code and the action are the recorded ones of HlFed, the controller runs at
+// that code, and neglogp and entropy of both heads go to HlFed::out; the LSTM state is what L.cs, L.hs hold on entry and stays there (state, reset,
+// actions, code_out: unused).  A code outside 0..255 reads nothing out of range and makes the four values of that row NaN.
+template <int OFF, bool PG = false, bool FED = false, class WT, class RM>
 __device__ __forceinline__ void hl_mid(const WT& W, HlLds& L, const float* __restrict__ obs, int stride, const uint8_t* __restrict__ reset, float* __restrict__ state,
                                        int sdim, int soff, float* __restrict__ actions, int32_t* __restrict__ code_out, const RM& R, int wave, int lane, int tid,
-                                       const HlPg& g = HlPg()) {
+                                       const HlPg& g = HlPg(), const HlFed& f = HlFed()) {
+  static_assert(PG || !FED, "the fed heads are the PPO actor's");
+  constexpr int AZ = OFF ? 1 : 0;                                                                  // the z code's column of A: behind SEPMC's heading
   float *b0 = L.big, *b1 = L.big + 256 * POL_M;
-  hl_load_state(state, sdim, soff, reset, R, L.cs, L.hs, tid);
+  if constexpr (!FED) hl_load_state(state, sdim, soff, reset, R, L.cs, L.hs, tid);
   hl_percepts(W, OFF + 49, obs, stride, R, L.big, L.feat, 32, tid);                                // usr_cmd_encoder: e2d | e1d | efr at 32..119
   pol_dense(L.vin, 3, W.a[OFF + 73], W.a[OFF + 74], 32, L.feat, 1, wave, lane);                   //                  vec at 0..31
   pol_dense(L.xs, 135, W.a[OFF + 47], W.a[OFF + 48], 64, b1, 1, wave, lane);                      // mlc_encoder prop embed: rows 0..63
@@ -277,10 +294,22 @@ __device__ __forceinline__ void hl_mid(const WT& W, HlLds& L, const float* __res
   __syncthreads();
   pol_dense(b1, 128, W.a[OFF + 77], W.a[OFF + 78], 256, b0, 1, wave, lane);                      // embed
   __syncthreads();
-  hl_lstm(W, OFF + 79, b0, b1, L.cs, L.hs, state, sdim, soff, R, wave, lane, tid);
+  hl_lstm<FED>(W, OFF + 79, b0, b1, L.cs, L.hs, state, sdim, soff, R, wave, lane, tid);
   pol_dense(L.hs, 32, W.a[OFF + 88], W.a[OFF + 89], 256, b0, 0, wave, lane);                     // z logits
   __syncthreads();
-  if constexpr (PG) {   // first maximum of logit (+ Gumbel noise when sampling) per row; max and sum of exp of 16 logits for the logsumexp
+  if constexpr (FED) {  // max and sum of exp of 16 logits in the PG branch's order, and (in L.pv, which holds no maximum here) the sum of exp x logit for the entropy
+    if (tid < 256) {
+      const int m = tid & 15, part = tid >> 4;
+      float mx = -3.0e38f, se = 0.0f, sw = 0.0f;
+      for (int q = 0; q < 16; q++) mx = fmaxf(mx, b0[(part * 16 + q) * POL_M + m]);
+      for (int q = 0; q < 16; q++) {
+        const float v = b0[(part * 16 + q) * POL_M + m], e = expf(v - mx);
+        se += e;
+        sw += e * v;
+      }
+      g.pm[part * POL_M + m] = mx; g.ps[part * POL_M + m] = se; L.pv[part * POL_M + m] = sw;
+    }
+  } else if constexpr (PG) {   // first maximum of logit (+ Gumbel noise when sampling) per row; max and sum of exp of 16 logits for the logsumexp
     if (tid < 256) {
       const int m = tid & 15, part = tid >> 4;
       float mx = -3.0e38f, se = 0.0f, bv = -3.0e38f;
@@ -315,7 +344,30 @@ __device__ __forceinline__ void hl_mid(const WT& W, HlLds& L, const float* __res
     if (tid < 256) { L.pv[part * POL_M + m] = bv; L.pi[part * POL_M + m] = bi; }
   }
   __syncthreads();
-  if (tid < POL_M) {
+  if constexpr (FED) {
+    if (tid < POL_M) {                                                                            // the recorded code; L.pi[row]: it is one
+      const bool live = R.live(tid);
+      const float cf = live ? f.a[(long)R.row(tid) * f.astride + AZ] : 0.0f;
+      const bool ok = cf >= 0.0f && cf < 256.0f;                                                  // (a NaN is neither)
+      const int bi = ok ? (int)cf : 0;
+      L.best[tid] = bi;
+      L.pi[tid] = ok ? 1 : 0;
+      if (live) {                                                                                 // logsumexp as below; entropy = logsumexp - sum softmax x logit
+        float mx = g.pm[tid];
+        for (int p = 1; p < 16; p++) mx = fmaxf(mx, g.pm[p * POL_M + tid]);
+        float se = 0.0f, sw = 0.0f;
+        for (int p = 0; p < 16; p++) {
+          const float w = expf(g.pm[p * POL_M + tid] - mx);
+          se += g.ps[p * POL_M + tid] * w;
+          sw += L.pv[p * POL_M + tid] * w;
+        }
+        const float lse = mx + logf(se), nan = __builtin_nanf("");
+        float* o = f.out + (long)R.row(tid) * f.ostride;
+        o[g.nh - 2] = ok ? lse - b0[bi * POL_M + tid] : nan;
+        o[2 * g.nh - 2] = ok ? lse - sw / se : nan;
+      }
+    }
+  } else if (tid < POL_M) {
     float bv = L.pv[tid];
     int bi = L.pi[tid];
     for (int p = 1; p < 16; p++)
@@ -347,7 +399,32 @@ __device__ __forceinline__ void hl_mid(const WT& W, HlLds& L, const float* __res
   __syncthreads();
   pol_dense(b0, 256, W.a[OFF + 99], W.a[OFF + 100], 12, b1, 0, wave, lane);                      // mean action: rows 0..11 of b1
   __syncthreads();
-  if constexpr (PG) {
+  if constexpr (FED) {
+    if (tid < 64) {     // as below with eps = (a - mean) / exp(logstd) of the recorded action; entropy = 6 (1 + log 2 pi) + sum logstd
+      const int grp = lane >> 4, m = lane & 15;
+      const bool live = R.live(m);
+      const float* a = f.a + (long)R.row(m) * f.astride + AZ + 1;
+      float nl = 0.0f, sl = 0.0f;
+      if (grp < 3) {
+#pragma unroll
+        for (int q = 0; q < 4; q++) {
+          const int c = 4 * grp + q;
+          const float ls = W.a[OFF + 101][c];
+          const float eps = ((live ? a[c] : 0.0f) - b1[c * POL_M + m]) / expf(ls);
+          nl += 0.5f * eps * eps + ls;
+          sl += ls;
+        }
+      }
+      nl += __shfl(nl, lane + 16) + __shfl(nl, lane + 32);
+      sl += __shfl(sl, lane + 16) + __shfl(sl, lane + 32);
+      if (grp == 0 && live) {
+        float* o = f.out + (long)R.row(m) * f.ostride;
+        const bool ok = L.pi[m] != 0;
+        o[g.nh - 1] = ok ? nl + 0.5f * HL_LOG_2PI * LLH_ACT_DIM : __builtin_nanf("");
+        o[2 * g.nh - 1] = ok ? sl + 0.5f * (1.0f + HL_LOG_2PI) * LLH_ACT_DIM : __builtin_nanf("");
+      }
+    }
+  } else if constexpr (PG) {
     if (tid < 64) {     // wavefront 0, lane = group * 16 + row: a = mean + exp(logstd) eps (logstd: array OFF + 101), neglogp summed over the groups
       const int grp = lane >> 4, m = lane & 15, r = R.row(m);
       const bool live = R.live(m);
@@ -442,7 +519,8 @@ struct HlPgLds {
 
 // The value branch (epmc_net.py:226-244, sepmc_net.py:271-292) of 16 rows on the checkpoint's arrays 2..46 (EPMC) / 2..50 (SEPMC); its LSTM
 // state [max_rows][64] (c | h) in vstate, zeroed by reset like the policy's.  value[R.srow(m)] <- the value of the map's rows.
-template <int KIND, class WT, class RM>
+// ONCHIP (the scorer, hl_score.inc): the state is what V.cs, V.hs hold on entry and stays there (vstate, reset: unused).
+template <int KIND, bool ONCHIP = false, class WT, class RM>
 __device__ __forceinline__ void hl_value(const WT& W, HlVLds& V, const float* __restrict__ obs, int stride, const uint8_t* __restrict__ reset,
                                          float* __restrict__ vstate, float* __restrict__ value, const RM& R, int wave, int lane, int tid) {
   float *a = V.a, *b = V.b, *xs = V.b + 120 * POL_M;
@@ -461,7 +539,7 @@ __device__ __forceinline__ void hl_value(const WT& W, HlVLds& V, const float* __
     const int col = k < 5 ? 913 + k : (k < 20 ? 933 + k - 5 : (k < 27 ? 955 + k - 20 : 962 + k - 27));
     V.vin[k * POL_M + m] = R.live(m) ? obs[(long)r * stride + col] : 0.0f;
   }
-  hl_load_state(vstate, 64, 0, reset, R, V.cs, V.hs, tid);
+  if constexpr (!ONCHIP) hl_load_state(vstate, 64, 0, reset, R, V.cs, V.hs, tid);
   __syncthreads();
   float h;
   int kv;
@@ -476,7 +554,7 @@ __device__ __forceinline__ void hl_value(const WT& W, HlVLds& V, const float* __
     __syncthreads();
     pol_dense(a + 128 * POL_M, 256, W.a[34], W.a[35], 256, b, 2, wave, lane);        // fc3 of [fc1 | fc2], tanh -> b
     __syncthreads();
-    h = hl_lstm(W, 36, b, a, V.cs, V.hs, vstate, 64, 0, R, wave, lane, tid);
+    h = hl_lstm<ONCHIP>(W, 36, b, a, V.cs, V.hs, vstate, 64, 0, R, wave, lane, tid);
     kv = 45;
   } else {
     hl_percepts(W, 4, obs, stride, R, a, b, 0, tid);                               // mlc_usr_cmd_encoder: e2d | e1d | efr -> b rows 0..87
@@ -491,7 +569,7 @@ __device__ __forceinline__ void hl_value(const WT& W, HlVLds& V, const float* __
     __syncthreads();
     pol_dense(a + 128 * POL_M, 384, W.a[38], W.a[39], 256, b, 2, wave, lane);        // fc4 of [fc1 | fc2 | fc3], tanh -> b
     __syncthreads();
-    h = hl_lstm(W, 40, b, a, V.cs, V.hs, vstate, 64, 0, R, wave, lane, tid);
+    h = hl_lstm<ONCHIP>(W, 40, b, a, V.cs, V.hs, vstate, 64, 0, R, wave, lane, tid);
     kv = 49;
   }
   const int m = tid >> 5, j = tid & 31;
@@ -500,10 +578,13 @@ __device__ __forceinline__ void hl_value(const WT& W, HlVLds& V, const float* __
 }
 
 // The policy of hl_policy_kernel with its heads sampled / scored (HlPg) for the 16 rows of R: what blockIdx.y 0 of the PPO actor launch runs.
-template <int KIND, class WT, class RM>
+// FED (the scorer, hl_score.inc): one time step of a recorded unroll.  The heads are those of HlFed (hl_mid), the mid level's target is the recorded
+// heading, and the LSTM states are what L.cs, L.hs and f.hcs, f.hhs hold on entry and stay there; of the pointers, only obs is used.
+template <int KIND, bool FED = false, class WT, class RM>
 __device__ __forceinline__ void hl_pg_policy(const WT& W, const RM& R, HlPgLds& S, const float* __restrict__ obs, int stride, const uint8_t* __restrict__ reset,
                                              float* __restrict__ state, float* __restrict__ actions, int32_t* __restrict__ code_out, float* __restrict__ heading_out,
-                                             float* __restrict__ neglogp, uint64_t seed, uint64_t step, int sample, int wave, int lane, int tid) {
+                                             float* __restrict__ neglogp, uint64_t seed, uint64_t step, int sample, int wave, int lane, int tid,
+                                             const HlFed& f = HlFed()) {
   HlLds& L = S.u.P;
   HlPg g;
   g.seed = seed; g.step = step; g.sample = sample; g.neglogp = neglogp; g.pm = S.pm; g.ps = S.ps;
@@ -519,7 +600,7 @@ __device__ __forceinline__ void hl_pg_policy(const WT& W, const RM& R, HlPgLds& 
       L.vin[k * POL_M + m] = R.live(m) ? obs[(long)r * stride + 913 + k] : 0.0f;
     }
     __syncthreads();
-    hl_mid<0, true>(W, L, obs, stride, reset, state, 64, 0, actions, code_out, R, wave, lane, tid, g);
+    hl_mid<0, true, FED>(W, L, obs, stride, reset, state, 64, 0, actions, code_out, R, wave, lane, tid, g, f);
   } else {
     float *b0 = L.big, *b1 = L.big + 256 * POL_M;
     if (tid < 29 * POL_M) {                                      // percept_vec 913..917 | oppo_info 918..932 | flag_info 948..954 | with_flag 962..963
@@ -527,7 +608,7 @@ __device__ __forceinline__ void hl_pg_policy(const WT& W, const RM& R, HlPgLds& 
       const int col = k < 20 ? 913 + k : (k < 27 ? 948 + k - 20 : 962 + k - 27);
       L.vin[k * POL_M + m] = R.live(m) ? obs[(long)r * stride + col] : 0.0f;
     }
-    hl_load_state(state, 128, 0, reset, R, L.cs, L.hs, tid);
+    if constexpr (!FED) hl_load_state(state, 128, 0, reset, R, L.cs, L.hs, tid);
     __syncthreads();
     hl_percepts(W, 53, obs, stride, R, L.big, L.feat, 0, tid);
     pol_dense(L.xs, 135, W.a[51], W.a[52], 64, b1, 1, wave, lane);
@@ -538,10 +619,23 @@ __device__ __forceinline__ void hl_pg_policy(const WT& W, const RM& R, HlPgLds& 
     __syncthreads();
     pol_dense(b1, 192, W.a[83], W.a[84], 256, b0, 1, wave, lane);
     __syncthreads();
-    const float h = hl_lstm(W, 85, b0, b1, L.cs, L.hs, state, 128, 0, R, wave, lane, tid);
+    const float h = hl_lstm<FED>(W, 85, b0, b1, FED ? f.hcs : L.cs, FED ? f.hhs : L.hs, state, 128, 0, R, wave, lane, tid);
     const int m = tid >> 5, j = tid & 31, r = R.row(m);
     const float mu = fminf(fmaxf(hl_sum32(h * W.a[94][j]) + W.a[95][0], -HL_PI), HL_PI);   // the Gaussian head's mean, clipped to +-pi
-    if (j == 0) {   // heading = mu + exp(a96) eps, not clipped (a96, 'logvar' in sepmc_net.py, is the DiagGaussian's logstd half); the mid level's target
+    if constexpr (FED) {
+      if (j == 0) {   // eps = (heading - mu) / exp(a96) of the recorded heading, which is the mid level's target; entropy = 0.5 (1 + log 2 pi) + a96
+        const bool live = R.live(m);
+        const float ls = W.a[96][0], hd = live ? f.a[(long)r * f.astride] : 0.0f, eps = (hd - mu) / expf(ls);
+        L.vin[0 * POL_M + m] = cosf(hd);
+        L.vin[1 * POL_M + m] = sinf(hd);
+        L.vin[2 * POL_M + m] = live ? obs[(long)r * stride + 964] : 0.0f;
+        if (live) {
+          float* o = f.out + (long)r * f.ostride;
+          o[0] = 0.5f * eps * eps + 0.5f * HL_LOG_2PI + ls;
+          o[LLH_SEPMC_N_HEADS] = 0.5f * (1.0f + HL_LOG_2PI) + ls;
+        }
+      }
+    } else if (j == 0) {   // heading = mu + exp(a96) eps, not clipped (a96, 'logvar' in sepmc_net.py, is the DiagGaussian's logstd half); the mid level's target
       float eps[4] = {0.0f, 0.0f, 0.0f, 0.0f};
       if (sample) hl_normals4(seed, step, (uint32_t)r, HL_HEADING_SALT, eps);
       const float ls = W.a[96][0], hd = mu + expf(ls) * eps[0];
@@ -552,7 +646,7 @@ __device__ __forceinline__ void hl_pg_policy(const WT& W, const RM& R, HlPgLds& 
       if (neglogp && R.live(m)) neglogp[(long)r * LLH_SEPMC_N_HEADS] = 0.5f * eps[0] * eps[0] + 0.5f * HL_LOG_2PI + ls;
     }
     __syncthreads();
-    hl_mid<50, true>(W, L, obs, stride, reset, state, 128, 64, actions, code_out, R, wave, lane, tid, g);
+    hl_mid<50, true, FED>(W, L, obs, stride, reset, state, 128, 64, actions, code_out, R, wave, lane, tid, g, f);
   }
 }
 

@@ -633,5 +633,6 @@ typedef SepmcEngine<HipBackend> SEPMC_ENGINE;
 #include "hl_policy.inc"
 #include "hl_unroll.inc"
 #include "hl_league.inc"
+#include "hl_score.inc"
 #include "xfer_capi.inc"
 #endif  // LL_KERNELS_ONLY
