@@ -203,7 +203,9 @@ LL_HD M3<float> qmat(const Q4& q) {  // unit quaternion -> rotation (world <- bo
   R.m[6] = 2 * (xz - yw); R.m[7] = 2 * (yz + xw); R.m[8] = -x2 - y2 + z2 + w2;
   return R;
 }
-// rotation vector of a quaternion given as (vector part v, scalar w), shortest arc (scipy as_rotvec)
+// rotation vector of a quaternion given as (vector part v, scalar w), shortest arc (scipy as_rotvec).  (v, w) need not be of unit length where |v| = sin(angle / 2)
+// holds (mocap_finish hands in 1 + e.w).  v = 0 gives a zero of either sign, never a NaN: w = -0.0f is not below zero, so nothing flips, and atan2f(0, -0) = pi
+// makes s = 2 pi / sinf(pi) finite; the lane-varying form evaluates angle / sin(angle / 2) in the branch it discards and selects it away.
 LL_HD V3<float> rotvec_of(V3<float> v, float w) {
   if (w < 0.0f) { v.x = -v.x; v.y = -v.y; v.z = -v.z; w = -w; }
   float n = sqrtf(v.x * v.x + v.y * v.y + v.z * v.z);

@@ -99,11 +99,13 @@ struct Pmc {
   }
 
   // sin/cos for joint angles (|x| < ~1e3): two-constant Cody-Waite reduction to [-pi/4, pi/4] + minimax polynomials,
-  // ~1 ulp, branch-free -- no large-argument path, which the library sincosf would inline six times per substep
+  // ~1 ulp, branch-free -- no large-argument path, which the library sincosf would inline six times per substep.
+  // The two reduction steps are ONE rounding each (lm::nfma_): the high part has 23 significant bits, so kf * hi is inexact from k = 3 on, and as a separate
+  // product the reduction loses up to 3e-5 absolute at |x| ~ 1e3 (2.6e-7 at |x| <= 6.3) -- which -ffp-contract would otherwise decide per build.
   static LL_HD void sincos_joint(const L& ln, const F& x, F* s, F* c) {
     F kf = lm::rint_(x * 0.63661977236758134f);
-    F r = x - kf * 1.5707962512969971f;            // pi/2 high part (float)
-    r = r - kf * 7.5497894158615964e-08f;          // pi/2 low part
+    F r = lm::nfma_(kf, ln.lane_f(1.5707962512969971f), x);          // x - kf * (pi/2 high part, float)
+    r = lm::nfma_(kf, ln.lane_f(7.5497894158615964e-08f), r);        // ... - kf * (pi/2 low part)
     F r2 = r * r;
     F sp = r + r * r2 * (-0.16666654611f + r2 * (0.0083321608736f + r2 * (-0.00019515295891f)));
     F cp = ln.lane_f(1.0f) + r2 * (-0.5f + r2 * (0.041666645683f + r2 * (-0.0013887316255f + r2 * 0.000024433157117f)));
@@ -230,16 +232,19 @@ struct Pmc {
     return r;
   }
 
-  // 6x6 SPD Cholesky on the packed lower triangle a[i*(i+1)/2 + j], in place; d[i] = 1/L_ii
+  // 6x6 SPD Cholesky on the packed lower triangle a[i*(i+1)/2 + j], in place; d[i] = 1/L_ii -- really the reciprocal of the stored
+  // L_ii = sqrt(s), so that d[i] L_ii is 1 to 2 u (u = 2^-24; a 1-ulp reciprocal times its argument, rounded).  With d[i] = r = rsqrt(s), L_ii = s r the
+  // product s r^2 was 3 u from 1 on gfx950 and 4 u in the host build (tests/test_gpu_math_helpers.py).  fwd6 / bwd6 read d and the off-diagonal entries only:
+  // in the step kernels the stored L_ii is dead and 1 / sqrt(s) contracts to one v_rsq_f32 either way -- their code objects did not change with this.
   static LL_HD void chol6(float* a, float* d) {
     for (int i = 0; i < 6; i++) {
       for (int j = 0; j <= i; j++) {
         float s = a[i * (i + 1) / 2 + j];
         for (int k = 0; k < j; k++) s -= a[i * (i + 1) / 2 + k] * a[j * (j + 1) / 2 + k];
         if (i == j) {
-          float r = lm::rsqrt_(s);
-          d[i] = r;
-          a[i * (i + 1) / 2 + i] = s * r;
+          float l = lm::sqrt_(s);
+          d[i] = 1.0f / l;
+          a[i * (i + 1) / 2 + i] = l;
         } else {
           a[i * (i + 1) / 2 + j] = s * d[j];
         }
@@ -502,7 +507,7 @@ struct Pmc {
         // outside an edge or corner the rounded distance -- a sphere or a link's mid-span meets an edge with the normal through its centre)
       T ox = lm::max_(qx, zero), oy = lm::max_(qy, zero), oz = lm::max_(qz, zero);
       T e2 = ox * ox + oy * oy + oz * oz;
-      B outside = e2 > 0.0f;
+      B outside = e2 > 0.0f;        // (a point outside by less than 1.1e-19 has e2 below the smallest normal float, which the device flushes: it keeps the face's distance and normal)
       T e = lm::sqrt_(e2), ie = one / lm::max_(e, ln.lane_f(1e-30f));
       d = lm::sel(outside, e, d);
       n = mk3<T>(lm::sel(outside, sx * ox * ie, n.x), lm::sel(outside, sy * oy * ie, n.y), lm::sel(outside, sz * oz * ie, n.z));
