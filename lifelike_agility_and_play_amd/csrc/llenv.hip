@@ -635,5 +635,6 @@ typedef SepmcEngine<HipBackend> SEPMC_ENGINE;
 #include "hl_league.inc"
 #include "hl_score.inc"
 #include "hl_loss.inc"
+#include "hl_lstm.inc"
 #include "xfer_capi.inc"
 #endif  // LL_KERNELS_ONLY
