@@ -77,7 +77,10 @@ LL_HD bool eq_(int a, int b) { return a == b; }
                          // (profiles/r05_mfma_gram_ab.txt, one box): 344 fewer instructions per substep, and 0.1921 -> 0.1912 ms per control step at 4096 envs (0.5 %), EPMC 0.9 %, SEPMC 1.6 % SLOWER,
                          // the 256-register builds 8 - 10 % slower (the 16-register accumulator tuple costs them scratch; a lone wave does not hide the MFMA chain): off.  Kept as an experiment
 #endif
-#define CONE_LDS_AT 64        // row-scratch word where a row's cone cross scalars live during the substeps (16 lanes x 32 words; GpuLanes::cone_store)
+#ifndef PMC_FRONT_TRIM
+#define PMC_FRONT_TRIM 1   // the front half of the substep without what the compiler adds for nothing (pmc_params.hpp); here: rmin / submin as one DPP instruction per stage.  0: as before, the A/B leg
+#endif
+#define CONE_LDS_AT 64       // row-scratch word where a row's cone cross scalars live during the substeps (16 lanes x 32 words; GpuLanes::cone_store)
 #define PMC_ROW_SCRATCH 688   // floats of LDS scratch per env row (EPMC: 40 boxes x 8, three ray lists of 10, 16 and 12 records, 64 spare: epmc_step.hpp)
 
 #if defined(__HIPCC__)
@@ -108,6 +111,7 @@ struct GpuLanes {
   static constexpr bool kHoldLink = false;   // pmc_step.hpp own_link: re-read the own-link constants every substep
   static constexpr bool kPrefetchShapes = false;   // see WithShapePrefetch below
   static constexpr bool kSubPlan = false;          // see WithSubPlan below
+  static constexpr bool kFrontTrim = false;        // see WithFrontTrim below
   LL_D GpuLanes(float* lds) : leg_((threadIdx.x >> 2) & 3), sub_(threadIdx.x & 3), lane16_(threadIdx.x & 15), lds_(lds), cbase_(0), tbase_(0) {}
 
   // Stage the constant tables in LDS: legc [n_leg_fields][4] then candc [n_cand_words][16].  A constant then costs one
@@ -216,6 +220,27 @@ struct GpuLanes {
   }
   LL_D float peer_u(float x) const { return peer(x); }
   // minimum over the 16 lanes of the row
+#if PMC_FRONT_TRIM
+  // One v_min_f32_dpp per stage.  Left to the compiler, fminf(y, DPP move of y) is three instructions a stage: the move, a canonicalising v_max_f32 m, m, m (fminf must quiet a
+  // signalling NaN, and the compiler cannot know what the moved register holds) and the v_min_f32.  The moved value is the same variable one stage earlier -- an arithmetic
+  // result or a constant, canonical already, flushed like any other operand by the v_min_f32 itself, and never a NaN in a step that passes its non-finite guard -- so the
+  // canonicalisation changes no bit.  Two wait states ahead of every stage: a DPP read of a VGPR the previous VALU instruction wrote.
+  // (the first stage writes a register of its own: a caller that goes on using x keeps it without a copy)
+#define LL_MIN0(CTRL) "s_nop 1\n\tv_min_f32_dpp %0, %1, %1 " CTRL " row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t"
+#define LL_MIN1(CTRL) "s_nop 1\n\tv_min_f32_dpp %0, %0, %0 " CTRL " row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t"
+  static LL_D float rmin(F x) {
+    float y;
+    asm(LL_MIN0("quad_perm:[1,0,3,2]") LL_MIN1("quad_perm:[2,3,0,1]") LL_MIN1("row_ror:4") LL_MIN1("row_ror:8") : "=v"(y) : "v"(x));
+    return y;
+  }
+  static LL_D F submin(F x) {
+    float y;
+    asm(LL_MIN0("quad_perm:[1,0,3,2]") LL_MIN1("quad_perm:[2,3,0,1]") : "=v"(y) : "v"(x));
+    return y;
+  }
+#undef LL_MIN1
+#undef LL_MIN0
+#else
   static LL_D float rmin(F x) {
     float y = fminf(x, LL_DPP_MOV(x, 0xB1));
     y = fminf(y, LL_DPP_MOV(y, 0x4E));
@@ -226,6 +251,7 @@ struct GpuLanes {
     float y = fminf(x, LL_DPP_MOV(x, 0xB1));
     return fminf(y, LL_DPP_MOV(y, 0x4E));
   }
+#endif
   // six row sums (all 16 lanes) at once; the DPP adds are interleaved so that no DPP read follows its producer by less
   // than two instructions (the compiler's own sequence pays an s_nop per DPP op)
 #define LL_STEP6(CTRL)                                                                         \
@@ -841,6 +867,14 @@ template <class Base, bool ON>
 struct WithSubPlan : Base {
   using Base::Base;
   static constexpr bool kSubPlan = ON;
+};
+
+// The substep's candidate evaluation and contact selection in their trimmed form (pmc_params.hpp PMC_FRONT_TRIM; pmc_step.hpp substep_impl).  Same arithmetic, bit for bit; asked for
+// by the multi-step one-wave-per-SIMD PMC kernels, which were measured.  The other kernels keep the code they had.
+template <class Base, bool ON>
+struct WithFrontTrim : Base {
+  using Base::Base;
+  static constexpr bool kFrontTrim = ON;
 };
 
 // The sixteen turn masks of a substep's solve as sixteen compares of the lane id instead of sixteen 64-bit constants: the compiler parks the constants in a spill register once

@@ -80,6 +80,10 @@ typedef GpuLanesPinned<LC_COUNT> GpuLanes1;                   // the per-leg tab
 #ifndef LL_TURN_MASKS_CMP_PMC1M
 #define LL_TURN_MASKS_CMP_PMC1M 1
 #endif
+// ... and run the trimmed front half of the substep (lanes.hpp WithFrontTrim, pmc_params.hpp PMC_FRONT_TRIM): the same kernels, by A/B against the parent build (profiles/front_trim_ab.txt)
+#ifndef LL_FRONT_TRIM_PMC1M
+#define LL_FRONT_TRIM_PMC1M PMC_FRONT_TRIM
+#endif
 #ifndef LL_GRAM_PIPE_PMC1
 #define LL_GRAM_PIPE_PMC1 0     // 1: the one-wave-per-SIMD PMC cone kernels form the Gram blocks of their contact rows on the matrix cores, one MFMA at a time between pieces of the next
                                 // row's arithmetic (lanes.hpp WithGramPipe; round 6, the round-5 review's "pipelined producer").  Built, held to the oracle on the host build, and measured
@@ -239,7 +243,8 @@ __global__ __launch_bounds__(PMC_WAVE, OCC) void pmc_step_kernel(StepParams P) {
   typedef WithParamsReload<typename std::conditional<OCC == 1, GpuLanesPmc1, GpuLanes>::type, LL_RELOAD_PMC> Lanes0;
   typedef typename std::conditional<(OCC == 2 && CONE && LL_CONE_LDS), WithConeInLds<Lanes0>, Lanes0>::type Lanes1;     // (launched with the row scratch allocated: launch_plan.hpp)
   typedef typename std::conditional<(OCC == 1 && MULTI && LL_TURN_MASKS_CMP_PMC1M), WithTurnMasksCmp<Lanes1>, Lanes1>::type Lanes2;
-  typedef WithSubPlan<Lanes2, (OCC == 1 && MULTI && LL_SUB_PLAN_PMC1M)> Lanes;
+  typedef WithSubPlan<Lanes2, (OCC == 1 && MULTI && LL_SUB_PLAN_PMC1M)> Lanes3;
+  typedef WithFrontTrim<Lanes3, (OCC == 1 && MULTI && LL_FRONT_TRIM_PMC1M)> Lanes;
   Lanes ln(lds);
   if constexpr (OCC == 1) ln.stage_consts(P.legc, LC_COUNT, P.candc, CAND_TABLE_WORDS, P.basec);   // all 64 lanes copy, also those without an env
   else ln.stage_consts(P.legc, LC_COUNT, P.candc, CAND_TABLE_WORDS);

@@ -106,7 +106,15 @@ enum BaseConst {
                                   // (lanes.hpp WithSubPlan; llenv.hip says which: decided per kernel by A/B).  0: every test fetches its argument, as before
 #endif
 
-#define LL_MAX_STEPS_PER_LAUNCH 128  // control steps one launch of ll_step_random_n runs at most (longer calls are split); sizes the per-step table slots
+#ifndef PMC_FRONT_TRIM
+#define PMC_FRONT_TRIM 1          // the compiler-scheduled half of the substep without the instructions that compute nothing the result needs.  Same floating-point operations on the same values
+                                  // in the same order: bit-identical.  lanes.hpp: rmin / submin as one DPP instruction per stage (every kernel).  pmc_step.hpp substep_impl, in the kernels whose
+                                  // lane policy asks for it (lanes.hpp WithFrontTrim; llenv.hip says which): the winner scan of the contact selection compares a key that only the winning lane
+                                  // holds, and on flat ground the candidate loop leans on the table's layout (pmc_tables.hpp pmc_check_cand_layout): the rim term once per cylinder, validity folded
+                                  // into the radius.  0: the source as it was, the A/B leg and the host test's reference
+#endif
+
+#define LL_MAX_STEPS_PER_LAUNCH 128 // control steps one launch of ll_step_random_n runs at most (longer calls are split); sizes the per-step table slots
 
 struct StepParams {
   static constexpr bool kFirstKernelArgument = true;   // every kernel takes it first, by value: lanes.hpp WithParamsReload re-reads it from the kernarg segment

@@ -404,6 +404,9 @@ struct Pmc {
     L::vel_commit2(d1, r1.lam, r1.ca01, r1.ca23, r1.cb01, r1.cj01, r1.cj23, d2, r2.lam, r2.ca01, r2.ca23, r2.cb01, r2.cj01, r2.cj23, VA, VB, VJ);   // (also lam += d)
   }
 
+  // does the lane policy take the trimmed front half of the substep (PMC_FRONT_TRIM)?  (lanes.hpp WithFrontTrim; a policy that does not say -- the host build's -- takes it)
+  template <class T, class = void> struct wants_front_trim { static constexpr bool value = true; };
+  template <class T> struct wants_front_trim<T, std::void_t<decltype(T::kFrontTrim)>> { static constexpr bool value = T::kFrontTrim; };
   template <int K_>
   static LL_HD void pick_rank(const L& ln, const F& rank, const F& me, const F& d, const F& sb, const F& jj, F& nd, F& ns, F& nj) {
     B take = lm::abs_(L::template subbcast<K_>(rank) - me) < 0.5f;
@@ -1312,9 +1315,28 @@ struct Pmc {
     F depth[NC];
     const bool want_touch = TERRAIN && ex && ex->want_touch;
     F tch_st = one, tch_fl = one;                             // 0 once a body link touches a static / the flag
+    // PMC_FRONT_TRIM, flat ground: what the table's layout settles is not computed again (pmc_tables.hpp pmc_check_cand_layout holds every table to it).  Only the two caps of a
+    // sub-lane's cylinder (group B) have an axis, and it is one axis: their rim term sqrt(max(0, 1 - (ez . ax)^2)) is formed once.  Every other candidate is a sphere or a
+    // vertex, ax = 0, for which that expression is sqrt(1) = 1 and r * 1 = r: the same depth, bit for bit.  A candidate the table marks invalid (link < 0; only outside group B)
+    // takes the radius -1e30 -- it floats 1e30 above the ground and fails the margin test by itself -- instead of a lane mask ANDed into every compare; the select is made from
+    // constants of the kernel, so it is made once.
+    constexpr bool TRIM = PMC_FRONT_TRIM != 0 && wants_front_trim<L>::value, TRIM_FLAT = TRIM && !TERRAIN;
+    F len_b = one;
+    if constexpr (TRIM_FLAT) {
+      V3l axb = mk3<F>(ln.candc(4 * CF_WORDS + CF_AX), ln.candc(4 * CF_WORDS + CF_AX + 1), ln.candc(4 * CF_WORDS + CF_AX + 2));
+      F azb = dot(gez[1], axb);
+      len_b = lm::sqrt_(lm::max_(one - azb * azb, zero));
+    }
     for (int jj = 0; jj < NT; jj++) {
       const int g = jj < 4 ? 0 : (jj < 6 ? 1 : (jj < 7 ? 2 : 0));   // (candidate 7 sits on group A's link)
       V3l A = mk3<F>(ln.candc(jj * CF_WORDS + CF_A), ln.candc(jj * CF_WORDS + CF_A + 1), ln.candc(jj * CF_WORDS + CF_A + 2));
+      if constexpr (TRIM_FLAT) {
+        F rj = ln.candc(jj * CF_WORDS + CF_R);
+        if (g != 1) rj = lm::sel(ln.candc(jj * CF_WORDS + CF_LINK) > -0.5f, rj, ln.lane_f(-1.0e30f));
+        F dj = g == 1 ? gz0[g] + dot(gez[g], A) - rj * len_b : gz0[g] + dot(gez[g], A) - rj;
+        depth[jj] = lm::sel(dj < P.margin_dist, dj, far_);
+        continue;
+      }
       V3l ax = mk3<F>(ln.candc(jj * CF_WORDS + CF_AX), ln.candc(jj * CF_WORDS + CF_AX + 1), ln.candc(jj * CF_WORDS + CF_AX + 2));
       F r = ln.candc(jj * CF_WORDS + CF_R), link = ln.candc(jj * CF_WORDS + CF_LINK);
       F az = dot(gez[g], ax);
@@ -1401,10 +1423,23 @@ struct Pmc {
       F wcode = L::submin(code);                            // lowest candidate index among them (1000 = none)
       B winner = lm::and_(code <= wcode, code < 500.0f);
       F dsel = zero;
-      for (int jj = 0; jj < NC; jj++) {
-        B hit = lm::and_(winner, lm::abs_(am - (float)jj) < 0.5f);
-        dsel = lm::sel(hit, depth[jj], dsel);
-        depth[jj] = lm::sel(hit, far_, depth[jj]);
+      if constexpr (TRIM) {
+        // am is a candidate's index jj exactly (the key of a candidate within the tolerance is clamped to jj from below; one outside it is jj + 100 -- a key strictly between
+        // would take two depths less than 1e-28 apart): only the winning lane keeps it, and a compare for equality with the constant finds the candidate -- no |am - jj| < 0.5
+        // and no AND with the winner's mask per candidate
+        const F amw = lm::sel(winner, am, ln.lane_f(-1.0f));
+        for (int jj = 0; jj < NC; jj++) {
+          const F cj = ln.lane_f((float)jj);
+          B hit = lm::not_(lm::or_(amw < cj, amw > cj));    // amw == jj, said with the comparisons every lane type has (amw is never a NaN: a minimum that starts from 100); one compare on the GPU
+          dsel = lm::sel(hit, depth[jj], dsel);
+          depth[jj] = lm::sel(hit, far_, depth[jj]);
+        }
+      } else {
+        for (int jj = 0; jj < NC; jj++) {
+          B hit = lm::and_(winner, lm::abs_(am - (float)jj) < 0.5f);
+          dsel = lm::sel(hit, depth[jj], dsel);
+          depth[jj] = lm::sel(hit, far_, depth[jj]);
+        }
       }
       F wdepth = L::subsum(dsel);
       F wsub = lm::rint_(wcode * (1.0f / STRIDE) - (0.5f - 0.5f / STRIDE));   // floor(wcode / STRIDE) for wcode = STRIDE sub + jj, jj <= STRIDE / 2

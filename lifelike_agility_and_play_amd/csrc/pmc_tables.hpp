@@ -161,6 +161,20 @@ static inline void pmc_cyl_cap(const PmcPrimView& p, int s, double* A, double* a
     A[c] = p.pos[c] + (s ? -1.0 : 1.0) * p.size[1] * ax[c];
   }
 }
+// What the flat-ground candidate loop takes from the layout instead of computing it per candidate and substep (pmc_step.hpp substep_impl, PMC_FRONT_TRIM): of a lane's seven
+// candidates only the two of group B (jj 4, 5: the caps of one cylinder) have an axis, both the same one, and both are valid; an invalid candidate (link < 0) sits outside group B.
+static inline std::string pmc_check_cand_layout(const std::vector<float>& t) {
+  for (int lane = 0; lane < 16; lane++)
+    for (int c = 0; c < 3; c++) {
+      for (int jj = 0; jj < 7; jj++)
+        if (jj != 4 && jj != 5 && t[(jj * CF_WORDS + CF_AX + c) * 16 + lane] != 0.0f) return "candidate table: a candidate outside group B has an axis";
+      if (t[(4 * CF_WORDS + CF_AX + c) * 16 + lane] != t[(5 * CF_WORDS + CF_AX + c) * 16 + lane]) return "candidate table: the two caps of group B differ in their axis";
+    }
+  for (int lane = 0; lane < 16; lane++)
+    for (int jj = 4; jj < 6; jj++)
+      if (t[(jj * CF_WORDS + CF_LINK) * 16 + lane] < 0.0f) return "candidate table: an invalid candidate in group B";
+  return "";
+}
 static inline std::string pmc_build_cand_table(const double* blob, std::vector<float>& t) {
   t.assign(CAND_TABLE_WORDS * 16, 0.0f);
   PmcPrimView bbox = pmc_prim(blob + LLM_OFF_BASE_PRIMS);
@@ -220,7 +234,7 @@ static inline std::string pmc_build_cand_table(const double* blob, std::vector<f
       }
     }
   }
-  return "";
+  return pmc_check_cand_layout(t);
 }
 
 // the ERPs as the kernel uses them, from what the spec switches say (LLM_SPEC_ERP, _LIMIT_ERP, _ERP_DEEP: "< 0" = follow the contact ERP / no second ERP)
