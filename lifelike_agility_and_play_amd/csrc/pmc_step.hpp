@@ -709,6 +709,26 @@ struct Pmc {
     }
     Pb = mulT(R, mk3<F>(Pw.x - bs.p.x, Pw.y - bs.p.y, Pw.z - bs.p.z));
   }
+  // One slot of the leg-leg pick: of the up to two capsule pairs a lane holds (cd: depth, 1e30 for none; cpair: the oracle's pair index, unique within the row; cP, cN: point and
+  // normal) the row takes the closest, pairs within LLM_SELECT_EPS of it counting as equally close and the lowest pair index winning.  have: there was one; cmin: its pair index;
+  // u6: its point and normal (sums over the row in which only the winning lane contributes); dsel: its own depth; its cd is overwritten with 1e30.
+  static LL_HD void self_pick(const L& ln, F* cd, const F* cpair, const V3l* cP, const V3l* cN, bool& have, float& cmin, float& dsel, float* u6) {
+    const F zero = ln.lane_f(0.0f), far_ = ln.lane_f(1.0e30f);
+    F dlane = lm::min_(cd[0], cd[1]);
+    float dmin = L::rmin(dlane);
+    B at0 = cd[0] <= ln.lane_f(dmin + (float)LLM_SELECT_EPS), at1 = cd[1] <= ln.lane_f(dmin + (float)LLM_SELECT_EPS);   // equally deep within the tolerance: lower pair index
+    F code = lm::min_(lm::sel(at0, cpair[0], ln.lane_f(1.0e9f)), lm::sel(at1, cpair[1], ln.lane_f(1.0e9f)));
+    cmin = L::rmin(code);
+    have = dmin < 1.0e29f;
+    B win0 = lm::and_(at0, lm::abs_(cpair[0] - cmin) < 0.5f), win1 = lm::and_(lm::and_(at1, lm::abs_(cpair[1] - cmin) < 0.5f), lm::not_(win0));
+    F w6[6];
+    w6[0] = lm::sel(win0, cP[0].x, lm::sel(win1, cP[1].x, zero)); w6[1] = lm::sel(win0, cP[0].y, lm::sel(win1, cP[1].y, zero));
+    w6[2] = lm::sel(win0, cP[0].z, lm::sel(win1, cP[1].z, zero)); w6[3] = lm::sel(win0, cN[0].x, lm::sel(win1, cN[1].x, zero));
+    w6[4] = lm::sel(win0, cN[0].y, lm::sel(win1, cN[1].y, zero)); w6[5] = lm::sel(win0, cN[0].z, lm::sel(win1, cN[1].z, zero));
+    L::rsum6(w6, u6);
+    dsel = have ? L::rmin(lm::sel(win0, cd[0], lm::sel(win1, cd[1], far_))) : 0.0f;   // the chosen pair's own depth (within the tolerance of dmin)
+    cd[0] = lm::sel(win0, far_, cd[0]); cd[1] = lm::sel(win1, far_, cd[1]);
+  }
   // closest points of the segments p1-q1 and p2-q2 (Ericson 5.1.9; same branches as the oracle's seg_seg)
   static LL_HD void seg_seg(const L& ln, const V3l& p1, const V3l& q1, const V3l& p2, const V3l& q2, V3l& c1, V3l& c2) {
     F s, t;
@@ -1714,21 +1734,9 @@ struct Pmc {
           if (slot >= SUB_MAX_SELF) break;                                             // (spec override LLM_SPEC_MAX_SELF)
           if (slot == 1 && !L::any(lm::min_(cd[0], cd[1]) < 1.0e29f)) break;        // nobody in the wave has a second one
           n_self_w = slot + 1;
-          F dlane = lm::min_(cd[0], cd[1]);
-          float dmin = L::rmin(dlane);
-          B at0 = cd[0] <= ln.lane_f(dmin + (float)LLM_SELECT_EPS), at1 = cd[1] <= ln.lane_f(dmin + (float)LLM_SELECT_EPS);   // equally deep within the tolerance: lower pair index
-          F code = lm::min_(lm::sel(at0, cpair[0], ln.lane_f(1.0e9f)), lm::sel(at1, cpair[1], ln.lane_f(1.0e9f)));
-          float cmin = L::rmin(code);
-          const bool have = dmin < 1.0e29f;
-          B win0 = lm::and_(at0, lm::abs_(cpair[0] - cmin) < 0.5f), win1 = lm::and_(lm::and_(at1, lm::abs_(cpair[1] - cmin) < 0.5f), lm::not_(win0));
-          F w6[6];
-          float u6[6];
-          w6[0] = lm::sel(win0, cP[0].x, lm::sel(win1, cP[1].x, zero)); w6[1] = lm::sel(win0, cP[0].y, lm::sel(win1, cP[1].y, zero));
-          w6[2] = lm::sel(win0, cP[0].z, lm::sel(win1, cP[1].z, zero)); w6[3] = lm::sel(win0, cN[0].x, lm::sel(win1, cN[1].x, zero));
-          w6[4] = lm::sel(win0, cN[0].y, lm::sel(win1, cN[1].y, zero)); w6[5] = lm::sel(win0, cN[0].z, lm::sel(win1, cN[1].z, zero));
-          L::rsum6(w6, u6);
-          const float dsel = have ? L::rmin(lm::sel(win0, cd[0], lm::sel(win1, cd[1], far_))) : 0.0f;   // the chosen pair's own depth (within the tolerance of dmin)
-          cd[0] = lm::sel(win0, far_, cd[0]); cd[1] = lm::sel(win1, far_, cd[1]);
+          bool have;
+          float cmin, dsel, u6[6];
+          self_pick(ln, cd, cpair, cP, cN, have, cmin, dsel, u6);
           // who is who: pair index -> (own leg: sign +, other leg: sign -) and the links (2 thigh, 3 shank)
           const int pair = have ? (int)(cmin + 0.5f) : 0, lpi = pair >> 2, spi = pair & 3;
           const int legA = lpi < 4 ? lpi : lpi - 4, legB = lpi < 4 ? ((lpi + 1) & 3) : lpi - 2;

@@ -64,8 +64,9 @@ for _k, _v in HELPERS.items():
     _v.setdefault('policies', [0]); _v.setdefault('targs', [0]); _v.setdefault('names', [_k])
 # LL_HD functions of pmc_math.hpp / listed members of Pmc<L> that no entry drives, each with the reason (test_math_helpers_emul.py: a function in neither table fails the scan)
 EXEMPT = {}
-# the members of Pmc<L> the scan asks for (the solver rows, finish_row, gs_round, the cone round and the contact builders are held one by one in solver_rows_common.py;
-# still open, listed there as LATER: leg_edge / reverse_edge and the candidate scan and contact selection inside substep_impl)
+# the members of Pmc<L> the scan asks for (the solver rows, finish_row, gs_round, the cone round and the contact builders are held one by one in solver_rows_common.py,
+# the terrain-edge detectors leg_edge / reverse_edge and one slot of the leg-leg pick, self_pick, in contact_scan_common.py; still open, listed there as LATER: the
+# deepest-K selection of the ground contacts, the candidate depth loop and the geometry of the leg-leg and robot-robot scans inside substep_impl)
 PMC_MEMBERS = ['sincos_joint', 'leg_fk', 'foot_world', 'own_link_inertia', 'link_inertia', 'damping_force', 'chol6', 'fwd6', 'bwd6', 'lm_fwd', 'lm_bwd', 'shape_sdf_rec',
                'terrain_sdf_rec', 'seg_seg_st', 'plane_space', 'row_bias', 'clip1', 'mocap_gather', 'mocap_finish']
 

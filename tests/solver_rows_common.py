@@ -82,8 +82,9 @@ PMC_MEMBERS = ['permute4', 'finish_row', 'cross_gram', 'contact_row', 'row_coeff
                'contact_rows_cone_piped', 'gs_round', 'gs_cone_round', 'pd_target', 'pd_torque', 'clip_velocities', 'pick_rank', 'self_row_clear', 'self_row_pack',
                'self_row_velocity', 'self_row_apply', 'self_turn', 'self_fric_turn', 'self_row_build', 'pair_row_build', 'pair_turn', 'pair_fric_turn', 'cand_eval_point']
 # ... and what stays for a later layer, each with the reason
+# (the terrain-edge detectors leg_edge / reverse_edge and one slot of the leg-leg pick, self_pick, are held in contact_scan_common.py, which also lists what is still open
+#  there: the deepest-K selection of the ground contacts)
 LATER = {
-    'leg_edge': 'geometry of the leg-leg detection, inside substep_impl', 'reverse_edge': 'as leg_edge',
     'substep_impl': 'the candidate scan, contact selection and the composition of the rounds: held end to end by the step parity tests',
 }
 
